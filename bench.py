@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — GCMC+FGCN SpMM edges/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: `value`, `ms_per_step`, `config`,
+`kernels` and `roofline` from the HIP events of the timed steps (at N > 1: the primary weak-scaling reading).
+`--full` adds everything that takes runs of its own: the probes behind `roofline.l2_gather`, `variants`,
+`edge_dropped_step`, `graph_construction`, `model_steps`, `cpu_baseline`, and at N > 1 the other weak-scaling
+reading.  `--dump-outputs DIR` writes what the 8 products of the last timed step returned as DIR/<product>.npy
+(float32, a fixed sample of DUMP_ROWS rows each; the inputs are seeded, so runs with the same arguments compare).
 
 `python bench.py --gpus N` with N > 1 and no launcher (WORLD_SIZE unset) starts its N ranks itself
 (`self_launch`: N fresh child processes of this file with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, spawned
@@ -23,8 +30,8 @@ pass of the message-passing hot path over those graphs, forward and backward:
 
 N > 1 (BASELINE config 5, weak scaling): SURVEY.md §8(d) fixes config 5 as N x the nodes AND N x
 the edges of config 4 (800k x 400k / 80 M edges at N = 8) — that is the primary workload; the
-other reading (config 4's node set with N x the edges) is measured in the same run with equal
-standing and reported under `edge_scaled` (`--scale edges` swaps the two).  Every rank owns a
+other reading (config 4's node set with N x the edges) is measured with --full, in the same run with equal
+standing, and reported under `edge_scaled` (`--scale edges` swaps the two).  Every rank owns a
 contiguous block of destination rows of every graph — cut by nnz (`balanced_row_bounds`) — and all
 their in-edges; each local SpMM is followed by the exchange of its row block over RCCL
 (dream_gnn_amd/shard.py: one RCCL all-gather per product — the default, and the only form the judged reading
@@ -37,13 +44,13 @@ The JSON line carries, besides the contract fields:
                 bytes / HIP-event time (the contract's definition — re-reads served by L2 / Infinity
                 Cache count, so `frac` may exceed 1), `traffic` = fabric bytes per launch from the
                 committed rocprofv3 PMC passes, and bounded readings beside it: `hbm_traffic_frac`
-                (measured bytes / time / HBM peak), `l2_gather` (the same product against the
+                (measured bytes / time / HBM peak), `l2_gather` (--full: the same product against the
                 row-gather rate a probe kernel reaches in this process, in the kernel's own access
                 shape and L2 regime), `compulsory_bytes`.
   kernels       per product: time, edges/s, algorithmic and compulsory bytes, both fractions.
-  variants      config-4-sized Zipf(1.2) product, the edge-dropped products the training step runs
+  variants      (--full) config-4-sized Zipf(1.2) product, the edge-dropped products the training step runs
                 (train.py:267), config 2 / 3 products as us per call.
-  cpu_baseline  the OpenMP CPU oracle timed on this box's host cores on a bounded sample.
+  cpu_baseline  (--full) the OpenMP CPU oracle timed on the host's cores on a bounded sample.
 """
 from __future__ import annotations
 
@@ -185,6 +192,37 @@ def build_ops(torch, rank, world, dev, scale):
     torch.cuda.synchronize()
     build_ms["kernel layouts (first product of each graph)"] = (time.perf_counter() - t0) * 1e3
     return ops, build_ms, (nd, ns, E, knn_k)
+
+
+def native_up_to_date():
+    """True when `make -q` finds nothing to rebuild in either native directory (it runs no recipe and writes nothing)."""
+    import subprocess
+
+    for sub, extra in ((("dream_gnn_amd", "csrc"), ["ARCH=gfx950"]), (("oracle",), [])):
+        cmd = ["make", "-q", "-s", "-C", os.path.join(ROOT, *sub)] + extra
+        if subprocess.call(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) != 0:
+            return False
+    return True
+
+
+DUMP_ROWS = 8192  # rows kept per product by --dump-outputs: 8 x 8192 x F x 4 B = 32 MB in all
+
+
+def dump_outputs(torch, ops, out_dir):
+    """--dump-outputs: each product's Y as its caller receives it (the whole row range: the exchanged Y at N > 1),
+    DUMP_ROWS rows of it drawn by a fixed seed, as float32 DIR/<product>.npy."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for op in ops:
+        y = op.y_local if op.y_full is None else op.y_full
+        n = y.shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_ROWS), replace=False))
+        sample = y.index_select(0, torch.from_numpy(rows).to(y.device)).float().cpu().numpy()
+        name = re.sub(r"[^0-9A-Za-z]+", "_", op.name.replace("->", "_to_"))
+        np.save(os.path.join(out_dir, name + ".npy"), sample)
 
 
 def run_step(torch, ops, comm_stream, record, exchange=None):
@@ -727,18 +765,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)   # >= 50 launches per product after >= 10 warm-ups
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra products and probes (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: probes, variants, edge-dropped step, graph construction, "
+                         "model steps, CPU baseline, and at N > 1 the other weak-scaling reading")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed row sample of each product of the last timed step as DIR/<product>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra products and probes")
     ap.add_argument("--scale", choices=["nodes", "edges"], default="nodes",
                     help="what grows with N in the primary run: nodes and edges (SURVEY §8d's config 5, default) "
-                         "or edges over config 4's node set; the other one is measured too")
+                         "or edges over config 4's node set; --full measures the other one too")
     args = ap.parse_args()
 
     # Native pieces first: make decides freshness, children are spawned before this process
     # touches the GPU (and before a profiler-preloaded runtime is initialised any further).
-    import __graft_entry__
+    # Libraries that build() left fresh are used as they are: the benchmark may run as a user
+    # who cannot write to the tree, where ensure_built()'s lock file cannot be created.
+    if not os.environ.get("DGMI_SKIP_BUILD") and not native_up_to_date():
+        import __graft_entry__
 
-    __graft_entry__.ensure_built()
+        __graft_entry__.ensure_built()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: what RCCL / device-tensor sharing needs on this stack
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -844,10 +890,13 @@ def main():
     exchange, exchange_timing = pick_exchange(ops)
     elapsed, edges_per_step = measure(ops, args.steps, args.warmup, exchange=exchange)
     progress("timed region done: %.3f ms per step" % (elapsed / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, ops, args.dump_outputs)
+        progress("outputs of the last timed step written to %s" % args.dump_outputs)
     primary_reading = reading(ops, elapsed, edges_per_step, args.steps, exchange) if world > 1 else None
 
     # per-kernel HIP-event time on the launch stream (rank 0's launches)
-    probes = probe_rates(torch, dev) if (world == 1 and not args.no_variants) else None
+    probes = probe_rates(torch, dev) if (world == 1 and args.full and not args.no_variants) else None
 
     def l2_roof(op):
         """The probe rate of the regime this product's gather runs in (GB/s), or None."""
@@ -888,7 +937,7 @@ def main():
                 dom_roofs.append(roof)
 
     other = None
-    if world > 1:  # the other weak-scaling reading, same run, equal standing
+    if world > 1 and args.full:  # the other weak-scaling reading, same run, equal standing
         alt = "nodes" if args.scale == "edges" else "edges"
         del ops
         torch.cuda.empty_cache()
@@ -982,7 +1031,7 @@ def main():
             out["probes_GBps"] = probes
         if other is not None:
             out["edge_scaled" if args.scale == "nodes" else "node_scaled"] = other
-        if world == 1 and not args.no_variants:
+        if world == 1 and args.full and not args.no_variants:
             progress("variants, edge-dropped step, model steps (context beside the judged step)")
             try:  # extra products beside the judged step: a failure here must not cost the line
                 out["variants"] = variants(torch, dev, ops)
@@ -997,7 +1046,7 @@ def main():
             except Exception as exc:  # noqa: BLE001
                 out["graph_construction"] = {"error": repr(exc)}
             out["model_steps"] = model_steps_in_child()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             progress("cpu_baseline (bounded sample on the host cores)")
             try:
                 out["cpu_baseline"] = cpu_baseline(torch, ops)

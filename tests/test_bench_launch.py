@@ -56,3 +56,20 @@ def test_under_a_launcher_the_world_size_must_match():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", DGMI_SKIP_BUILD="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 4" in (r.stderr + r.stdout)
+
+
+def test_a_built_tree_is_used_without_writing_to_it():
+    """After build(), bench.py and ensure_built() find nothing to make and take no lock file in the tree: the benchmark
+    may run as a user who cannot write to it."""
+    import importlib.util
+
+    import __graft_entry__
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    lock = os.path.join(ROOT, ".build.lock")
+    before = os.stat(lock).st_mtime_ns if os.path.exists(lock) else None
+    assert __graft_entry__.up_to_date() and bench.native_up_to_date()
+    __graft_entry__.ensure_built()
+    assert (os.stat(lock).st_mtime_ns if os.path.exists(lock) else None) == before

@@ -119,7 +119,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update({"DGMI_DIST_BACKEND": "gloo", "DGMI_BENCH_LAUNCH_TIMEOUT": "420"})
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=480, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=480, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0
