@@ -1,0 +1,472 @@
+// dgmi_pairs.hip — all-pairs MLP decoder with an on-chip top-k (gfx950): the model's novel-pair ranking.
+//
+// Replaces the scoring loop of the reference's get_top_novel_predictions (train.py:26-151): every drug-disease pair
+// (i, j) that is not a known association gets
+//     logit(i, j) = b3 + sum_h w3[h] relu(b2[h] + sum_k W2[h, k] relu(P[i, k] + Q[j, k])),   h < 64, k < 128,
+// where P = hd W1a^T + b1 and Q = hs W1b^T are the split first decoder layer (model.MLPDecoder.fuse_lin1), and the k
+// best (logit desc, then (i, j) asc) are returned.  The n_drug x n_dis x 128 hidden layer is never written.
+//
+// Scorer.  A wave owns 32 diseases (one per lane column) and walks drugs two at a time.  For drug i the 64 x 32 block
+// W2 . relu(P[i] + Q[j0:j0+32]) is 2 x 64 `v_mfma_f32_32x32x2_f32` (f32 in, f32 accumulate: exact f32 arithmetic):
+// A = W2 rows (lane l: row l & 31 of the half, k = 64 (l >> 5) + s at step s), B = relu(P[i, k] + Q[j, k]) with the
+// same k and the pair on the lane column.  The lane's 64 Q values and 128 W2 values stay in VGPRs for the whole kernel
+// (Q: per task), P rows come from LDS as a two-address broadcast.  Two drugs x two row halves = 4 independent
+// accumulators per wave, the condition for the 64-cycle f32 MFMA to issue back to back from one wave per SIMD.
+// After the 64 steps each lane sums w3[h] relu(acc + b2[h]) over its 32 rows and adds its partner lane (l ^ 32).
+//
+// Top-k.  A persistent grid of one workgroup per CU takes (drug chunk, 128-disease group) tasks in drug-major order,
+// so all workgroups read the same P rows at the same time.  Each keeps, in LDS, its best-k list followed by an append
+// buffer: a lane whose pair beats the workgroup's threshold (the k-th key of its list) appends it at its ballot rank.
+// Every 4 drugs the workgroup checks the fill; past 3/4 it sorts list + buffer (bitonic, on the full key) and raises
+// the threshold.  A merge kernel reduces the workgroups' sorted lists in rounds of up to 64 lists to the result.
+// Every comparison is on the full key (logit, i, j), so the result does not depend on scheduling.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "dgmi.h"
+#include "dgmi_pairs.h"
+
+namespace {
+
+constexpr int kH1 = 128;                 // decoder hidden width 1 (layers.py:349)
+constexpr int kH2 = 64;                  // decoder hidden width 2 (layers.py:350)
+constexpr int kThreads = 256;            // 4 waves; each owns 32 diseases of the task's group
+constexpr int kGroupCols = 128;          // diseases per task
+constexpr int kMaxChunk = 64;            // drugs per task (at most)
+constexpr int kPStride = 2 * 68;         // a P row in LDS: two 64-float halves, 4 floats apart (conflict-free broadcast)
+constexpr int kSortCap = 2048;           // LDS list + append buffer, entries
+constexpr int kSub = 4;                  // drugs between two fill checks: at most kSub * kGroupCols appends
+constexpr int kGrid = 256;               // persistent workgroups (one per CU)
+constexpr int kMergeThreads = 1024;
+constexpr int kMergeCap = 8192;          // entries one merge workgroup sorts
+constexpr int kMaxFan = 64;
+constexpr size_t kAlign = 256;
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+// order-preserving key of a logit: larger logit -> larger key; NaN -> 0, below every number; -0 == +0
+__device__ __forceinline__ uint32_t order_key(float x) {
+  if (x != x) return 0u;
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float key_logit(uint32_t f) {
+  if (f == 0u) return __uint_as_float(0x7fc00000u);
+  return __uint_as_float((f & 0x80000000u) ? (f & 0x7fffffffu) : ~f);
+}
+
+// the full ranking key: logit descending, then drug ascending, then disease ascending
+__device__ __forceinline__ bool better(uint32_t fa, uint32_t ia, uint32_t ja, uint32_t fb, uint32_t ib, uint32_t jb) {
+  return fa > fb || (fa == fb && (ia < ib || (ia == ib && ja < jb)));
+}
+
+// relu that keeps NaN (torch.relu does; fmaxf would drop it)
+__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
+
+// Bitonic sort of n (a power of two) entries of the SoA list (f, i, j) into descending key order, all threads of the
+// block.  Ends with a barrier.
+__device__ void block_sort_desc(uint32_t* f, uint32_t* ii, uint32_t* jj, int n, int tid, int nthr) {
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (n >> 1); t += nthr) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const uint32_t fl = f[lo], fh = f[hi], il = ii[lo], ih = ii[hi], jl = jj[lo], jh = jj[hi];
+        if (better(fh, ih, jh, fl, il, jl) == desc) {
+          f[lo] = fh;
+          f[hi] = fl;
+          ii[lo] = ih;
+          ii[hi] = il;
+          jj[lo] = jh;
+          jj[hi] = jl;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ void set_pad(uint32_t* f, uint32_t* ii, uint32_t* jj, int e) {
+  f[e] = 0u;  // below every candidate: a real NaN pair has the same key but smaller ids
+  ii[e] = 0xffffffffu;
+  jj[e] = 0xffffffffu;
+}
+
+// known[(i, j)] -> bit j & 31 of word i * nwords + j / 32; an id outside its range sets info[1]
+__global__ __launch_bounds__(256) void known_bitmap_kernel(const int32_t* __restrict__ kd, const int32_t* __restrict__ ks,
+                                                           int64_t n_known, int n_drug, int n_dis, int64_t nwords,
+                                                           uint32_t* __restrict__ bitmap, int32_t* __restrict__ info) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_known; e += (int64_t)gridDim.x * 256) {
+    const int32_t i = kd[e], j = ks[e];
+    if (i < 0 || i >= n_drug || j < 0 || j >= n_dis) {
+      atomicOr(&info[1], 1);
+      continue;
+    }
+    atomicOr(&bitmap[(int64_t)i * nwords + (j >> 5)], 1u << (j & 31));
+  }
+}
+
+struct ScoreArgs {
+  const float* P;
+  int64_t ldp;
+  const float* Q;
+  int64_t ldq;
+  int n_drug, n_dis;
+  const float* W2;
+  const float* b2;
+  const float* w3;
+  const float* b3;
+  const uint32_t* bitmap;  // nullptr: nothing known
+  int64_t nwords;
+  int k, chunk, n_groups;
+  int64_t n_tasks;
+  uint32_t* list_f;  // [gridDim.x][k]
+  uint32_t* list_i;
+  uint32_t* list_j;
+  int32_t* list_n;   // [gridDim.x]
+};
+
+__global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
+  __shared__ __attribute__((aligned(16))) float p_lds[kMaxChunk * kPStride];
+  __shared__ uint32_t ef[kSortCap], ei[kSortCap], ej[kSortCap];
+  __shared__ int s_used;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int half = lane >> 5, col = lane & 31;
+  const int k = a.k;
+
+  // this lane's W2 operands (rows col and 32 + col, k = 64 half + s) and epilogue rows h = 32 hb + 8 (r >> 2) + 4 half + (r & 3)
+  float wa[kH1 / 2], wb[kH1 / 2];
+#pragma unroll
+  for (int s4 = 0; s4 < 16; ++s4) {
+    const float4 x = *reinterpret_cast<const float4*>(a.W2 + col * kH1 + 64 * half + 4 * s4);
+    const float4 y = *reinterpret_cast<const float4*>(a.W2 + (32 + col) * kH1 + 64 * half + 4 * s4);
+    wa[4 * s4] = x.x, wa[4 * s4 + 1] = x.y, wa[4 * s4 + 2] = x.z, wa[4 * s4 + 3] = x.w;
+    wb[4 * s4] = y.x, wb[4 * s4 + 1] = y.y, wb[4 * s4 + 2] = y.z, wb[4 * s4 + 3] = y.w;
+  }
+  float eb[2][16], ew[2][16];
+#pragma unroll
+  for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int h = 32 * hb + 8 * (r >> 2) + 4 * half + (r & 3);
+      eb[hb][r] = a.b2[h];
+      ew[hb][r] = a.w3[h];
+    }
+  const float bias3 = a.b3[0];
+
+  if (tid == 0) s_used = 0;
+  bool full = false;  // the list holds k entries: (tf, ti, tj) is its k-th key
+  uint32_t tf = 0u, ti = 0xffffffffu, tj = 0xffffffffu;
+
+  // sort list + buffer, keep the best k, raise the threshold.  Called by the whole block after a barrier.
+  auto select = [&]() {
+    const int n = s_used;
+    int np = 1;
+    while (np < n) np <<= 1;
+    for (int e = n + tid; e < np; e += kThreads) set_pad(ef, ei, ej, e);
+    __syncthreads();
+    block_sort_desc(ef, ei, ej, np, tid, kThreads);
+    const int keep = n < k ? n : k;
+    full = keep == k;
+    if (full) {
+      tf = ef[k - 1];
+      ti = ei[k - 1];
+      tj = ej[k - 1];
+    }
+    __syncthreads();  // everyone has read s_used and the threshold
+    if (tid == 0) s_used = keep;
+    __syncthreads();
+  };
+
+  // offer lane `col`'s pair (i, j) of one drug; lanes 32..63 hold the same pairs and never append
+  auto offer = [&](bool valid, float logit, uint32_t i, uint32_t j) {
+    const uint32_t f = order_key(logit);
+    const bool q = half == 0 && valid && (!full || better(f, i, j, tf, ti, tj));
+    const uint64_t m = __ballot(q);
+    if (m != 0) {
+      const int leader = __ffsll((unsigned long long)m) - 1;
+      int base = 0;
+      if (lane == leader) base = atomicAdd(&s_used, __popcll(m));
+      base = __shfl(base, leader);
+      if (q) {
+        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (pos < kSortCap) {  // always: at most kSub * kGroupCols appends between two checks
+          ef[pos] = f;
+          ei[pos] = i;
+          ej[pos] = j;
+        }
+      }
+    }
+  };
+
+  for (int64_t task = blockIdx.x; task < a.n_tasks; task += gridDim.x) {
+    const int g = (int)(task % a.n_groups);
+    const int i0 = (int)(task / a.n_groups) * a.chunk;
+    const int nd = a.n_drug - i0 < a.chunk ? a.n_drug - i0 : a.chunk;
+    __syncthreads();  // the previous task's readers of p_lds are done
+    for (int e = tid; e < a.chunk * 32; e += kThreads) {
+      const int r = e >> 5, c4 = e & 31;
+      const int row = r < nd ? i0 + r : a.n_drug - 1;
+      const float4 v = *reinterpret_cast<const float4*>(a.P + (int64_t)row * a.ldp + 4 * c4);
+      *reinterpret_cast<float4*>(p_lds + r * kPStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+    }
+    const int j0 = g * kGroupCols + wave * 32;  // this wave's 32 diseases
+    const int j = j0 + col;
+    const bool col_ok = j < a.n_dis;
+    const int jc = col_ok ? j : a.n_dis - 1;
+    float q[kH1 / 2];
+#pragma unroll
+    for (int s4 = 0; s4 < 16; ++s4) {
+      const float4 x = *reinterpret_cast<const float4*>(a.Q + (int64_t)jc * a.ldq + 64 * half + 4 * s4);
+      q[4 * s4] = x.x, q[4 * s4 + 1] = x.y, q[4 * s4 + 2] = x.z, q[4 * s4 + 3] = x.w;
+    }
+    const bool words = a.bitmap != nullptr && j0 < a.n_dis;
+    const uint32_t* bm = a.bitmap + (words ? (j0 >> 5) : 0);
+    __syncthreads();
+
+    for (int d0 = 0; d0 < nd; d0 += kSub) {
+      const int d_end = d0 + kSub < nd ? d0 + kSub : nd;
+      for (int da = d0; da < d_end; da += 2) {
+        const bool has_b = da + 1 < d_end;
+        const int db = has_b ? da + 1 : da;
+        const uint32_t kwa = words ? bm[(int64_t)(i0 + da) * a.nwords] : 0u;
+        const uint32_t kwb = words ? bm[(int64_t)(i0 + db) * a.nwords] : 0u;
+        const float* pa = p_lds + da * kPStride + 68 * half;
+        const float* pb = p_lds + db * kPStride + 68 * half;
+        floatx16 c00, c01, c10, c11;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) c00[v] = c01[v] = c10[v] = c11[v] = 0.f;
+#pragma unroll
+        for (int s4 = 0; s4 < 16; ++s4) {
+          const float4 xa = *reinterpret_cast<const float4*>(pa + 4 * s4);
+          const float4 xb = *reinterpret_cast<const float4*>(pb + 4 * s4);
+          const float va[4] = {xa.x, xa.y, xa.z, xa.w}, vb[4] = {xb.x, xb.y, xb.z, xb.w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int s = 4 * s4 + u;
+            const float ba = relu_nan(va[u] + q[s]);
+            const float bb = relu_nan(vb[u] + q[s]);
+            c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s], ba, c00, 0, 0, 0);
+            c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[s], ba, c01, 0, 0, 0);
+            c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s], bb, c10, 0, 0, 0);
+            c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[s], bb, c11, 0, 0, 0);
+          }
+        }
+        float sa = 0.f, sb = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          sa = fmaf(ew[0][r], relu_nan(c00[r] + eb[0][r]), sa);
+          sb = fmaf(ew[0][r], relu_nan(c10[r] + eb[0][r]), sb);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          sa = fmaf(ew[1][r], relu_nan(c01[r] + eb[1][r]), sa);
+          sb = fmaf(ew[1][r], relu_nan(c11[r] + eb[1][r]), sb);
+        }
+        const float la = (sa + __shfl_xor(sa, 32)) + bias3;
+        const float lb = (sb + __shfl_xor(sb, 32)) + bias3;
+        offer(col_ok && !((kwa >> col) & 1u), la, (uint32_t)(i0 + da), (uint32_t)j);
+        offer(has_b && col_ok && !((kwb >> col) & 1u), lb, (uint32_t)(i0 + db), (uint32_t)j);
+      }
+      __syncthreads();  // this period's appends are in
+      const int n = s_used;
+      __syncthreads();  // everyone has read the fill before anyone appends again
+      if (n > kSortCap - kSub * kGroupCols) select();
+    }
+  }
+
+  __syncthreads();
+  select();
+  const int keep = s_used;
+  uint32_t* of = a.list_f + (int64_t)blockIdx.x * k;
+  uint32_t* oi = a.list_i + (int64_t)blockIdx.x * k;
+  uint32_t* oj = a.list_j + (int64_t)blockIdx.x * k;
+  for (int e = tid; e < keep; e += kThreads) {
+    of[e] = ef[e];
+    oi[e] = ei[e];
+    oj[e] = ej[e];
+  }
+  if (tid == 0) a.list_n[blockIdx.x] = keep;
+}
+
+// One round of the final reduction: workgroup b merges lists [b fan, (b + 1) fan) of `n_lists` sorted lists into the
+// best k.  The last round (one workgroup) writes the result and its count.
+__global__ __launch_bounds__(kMergeThreads) void pair_merge_kernel(const uint32_t* __restrict__ in_f, const uint32_t* __restrict__ in_i,
+                                                                  const uint32_t* __restrict__ in_j, const int32_t* __restrict__ in_n,
+                                                                  int n_lists, int k, int fan, uint32_t* __restrict__ out_f,
+                                                                  uint32_t* __restrict__ out_i, uint32_t* __restrict__ out_j,
+                                                                  int32_t* __restrict__ out_n, int32_t* __restrict__ out_drug,
+                                                                  int32_t* __restrict__ out_dis, float* __restrict__ out_logit,
+                                                                  int32_t* __restrict__ out_info) {
+  extern __shared__ uint32_t merge_lds[];
+  __shared__ int s_total;
+  const int tid = threadIdx.x;
+  const int first = (int)blockIdx.x * fan;
+  const int nl = n_lists - first < fan ? n_lists - first : fan;
+  int np = 1;
+  while (np < nl * k) np <<= 1;
+  uint32_t* f = merge_lds;
+  uint32_t* ii = merge_lds + np;
+  uint32_t* jj = merge_lds + 2 * np;
+  if (tid == 0) {
+    int t = 0;
+    for (int l = 0; l < nl; ++l) t += in_n[first + l];
+    s_total = t;
+  }
+  for (int e = tid; e < np; e += kMergeThreads) {
+    const int l = e / k, p = e - l * k;
+    if (l < nl && p < in_n[first + l]) {
+      const int64_t src = (int64_t)(first + l) * k + p;
+      f[e] = in_f[src];
+      ii[e] = in_i[src];
+      jj[e] = in_j[src];
+    } else {
+      set_pad(f, ii, jj, e);
+    }
+  }
+  __syncthreads();
+  block_sort_desc(f, ii, jj, np, tid, kMergeThreads);
+  const int keep = s_total < k ? s_total : k;
+  if (out_drug != nullptr) {
+    for (int e = tid; e < keep; e += kMergeThreads) {
+      out_drug[e] = (int32_t)ii[e];
+      out_dis[e] = (int32_t)jj[e];
+      out_logit[e] = key_logit(f[e]);
+    }
+    if (tid == 0) out_info[0] = keep;
+  } else {
+    const int64_t o = (int64_t)blockIdx.x * k;
+    for (int e = tid; e < keep; e += kMergeThreads) {
+      out_f[o + e] = f[e];
+      out_i[o + e] = ii[e];
+      out_j[o + e] = jj[e];
+    }
+    if (tid == 0) out_n[blockIdx.x] = keep;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side
+
+inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
+
+struct Plan {
+  int chunk, n_groups, grid, fan;
+  int64_t n_tasks, nwords;
+  size_t bitmap, lists_a, lists_b, total;  // byte offsets / size
+};
+
+size_t lists_bytes(int64_t n_lists, int k) { return align_up((size_t)n_lists * (size_t)k * 12) + align_up((size_t)n_lists * 4); }
+
+Plan make_plan(int64_t n_drug, int64_t n_dis, int k) {
+  Plan p;
+  p.n_groups = (int)((n_dis + kGroupCols - 1) / kGroupCols);
+  // enough tasks for ~4 per workgroup on small problems; 64-drug chunks otherwise
+  p.chunk = kMaxChunk;
+  while (p.chunk > 2 && ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups < 4 * kGrid) p.chunk >>= 1;
+  p.n_tasks = ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups;
+  p.grid = (int)(p.n_tasks < kGrid ? p.n_tasks : kGrid);
+  int kp = 1;
+  while (kp < k) kp <<= 1;
+  p.fan = kMergeCap / kp;
+  if (p.fan > kMaxFan) p.fan = kMaxFan;
+  if (p.fan < 2) p.fan = 2;
+  p.nwords = (n_dis + 31) / 32;
+  p.bitmap = 0;
+  p.lists_a = align_up((size_t)n_drug * (size_t)p.nwords * 4);
+  p.lists_b = p.lists_a + lists_bytes(p.grid, k);
+  p.total = p.lists_b + lists_bytes((p.grid + p.fan - 1) / p.fan, k);
+  return p;
+}
+
+struct Lists {
+  uint32_t *f, *i, *j;
+  int32_t* n;
+};
+
+Lists lists_at(void* ws, size_t off, int64_t n_lists, int k) {
+  char* b = static_cast<char*>(ws) + off;
+  const size_t m = (size_t)n_lists * (size_t)k;
+  Lists l;
+  l.f = reinterpret_cast<uint32_t*>(b);
+  l.i = l.f + m;
+  l.j = l.i + m;
+  l.n = reinterpret_cast<int32_t*>(b + align_up(m * 12));
+  return l;
+}
+
+inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+}  // namespace
+
+extern "C" {
+
+DGMI_API size_t dgmi_pair_topk_workspace_bytes(int64_t n_drug, int64_t n_dis, int32_t k) {
+  if (n_drug <= 0 || n_dis <= 0 || n_drug > INT32_MAX || n_dis > INT32_MAX || k < 1 || k > DGMI_PAIR_TOPK_MAX_K) return 0;
+  return make_plan(n_drug, n_dis, k).total;
+}
+
+DGMI_API int dgmi_pair_mlp_topk_f32(const float* P, int64_t ldp, int64_t n_drug, const float* Q, int64_t ldq, int64_t n_dis,
+                                    int32_t h1, int32_t h2, const float* W2, const float* b2, const float* w3, const float* b3,
+                                    const int32_t* known_drug, const int32_t* known_dis, int64_t n_known, int32_t k,
+                                    int32_t* out_drug, int32_t* out_dis, float* out_logit, int32_t* out_info, void* workspace,
+                                    size_t workspace_bytes, dgmi_stream_t stream) {
+  if (h1 != kH1 || h2 != kH2 || k < 1 || k > DGMI_PAIR_TOPK_MAX_K) return DGMI_ERR_INVALID_ARG;
+  if (n_drug < 0 || n_dis < 0 || n_known < 0 || n_drug > INT32_MAX || n_dis > INT32_MAX) return DGMI_ERR_INVALID_ARG;
+  if (n_drug == 0 || n_dis == 0) return DGMI_OK;
+  if (P == nullptr || Q == nullptr || W2 == nullptr || b2 == nullptr || w3 == nullptr || b3 == nullptr || out_drug == nullptr ||
+      out_dis == nullptr || out_logit == nullptr || out_info == nullptr)
+    return DGMI_ERR_INVALID_ARG;
+  if (n_known > 0 && (known_drug == nullptr || known_dis == nullptr)) return DGMI_ERR_INVALID_ARG;
+  if (ldp < kH1 || ldq < kH1 || ldp % 4 != 0 || ldq % 4 != 0 || misaligned(P) || misaligned(Q) || misaligned(W2))
+    return DGMI_ERR_INVALID_ARG;
+  const Plan plan = make_plan(n_drug, n_dis, k);
+  if (workspace == nullptr || workspace_bytes < plan.total) return DGMI_ERR_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
+  uint32_t* bitmap = nullptr;
+  if (n_known > 0) {
+    bitmap = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + plan.bitmap);
+    if (hipMemsetAsync(bitmap, 0, (size_t)n_drug * (size_t)plan.nwords * 4, s) != hipSuccess) return DGMI_ERR_LAUNCH;
+    int64_t blocks = (n_known + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, known_drug, known_dis, n_known,
+                       (int)n_drug, (int)n_dis, plan.nwords, bitmap, out_info);
+  }
+
+  Lists la = lists_at(workspace, plan.lists_a, plan.grid, k);
+  ScoreArgs args{P, ldp, Q, ldq, (int)n_drug, (int)n_dis, W2, b2, w3, b3, bitmap, plan.nwords, k, plan.chunk,
+                 plan.n_groups, plan.n_tasks, la.f, la.i, la.j, la.n};
+  hipLaunchKernelGGL(pair_mlp_topk_kernel, dim3((unsigned)plan.grid), dim3(kThreads), 0, s, args);
+  if (hipGetLastError() != hipSuccess) return DGMI_ERR_LAUNCH;
+
+  const size_t lds = (size_t)kMergeCap * 12;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(pair_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return DGMI_ERR_LAUNCH;
+  // rounds: lists A -> B -> A ... until one workgroup merges what is left into the result
+  int n_lists = plan.grid;
+  bool in_a = true;
+  for (;;) {
+    const int out_lists = (n_lists + plan.fan - 1) / plan.fan;
+    const Lists src = in_a ? la : lists_at(workspace, plan.lists_b, (plan.grid + plan.fan - 1) / plan.fan, k);
+    const Lists dst = in_a ? lists_at(workspace, plan.lists_b, (plan.grid + plan.fan - 1) / plan.fan, k) : la;
+    const bool last = out_lists == 1;
+    int kp = 1;
+    while (kp < (n_lists < plan.fan ? n_lists : plan.fan) * k) kp <<= 1;
+    hipLaunchKernelGGL(pair_merge_kernel, dim3((unsigned)out_lists), dim3(kMergeThreads), (size_t)kp * 12, s, src.f, src.i,
+                       src.j, src.n, n_lists, k, plan.fan, dst.f, dst.i, dst.j, dst.n, last ? out_drug : nullptr, out_dis,
+                       out_logit, out_info);
+    if (hipGetLastError() != hipSuccess) return DGMI_ERR_LAUNCH;
+    if (last) break;
+    n_lists = out_lists;
+    in_a = !in_a;
+  }
+  return DGMI_OK;
+}
+
+}  // extern "C"

@@ -25,6 +25,7 @@
 #include <unordered_map>
 
 #include "dgmi.h"
+#include "dgmi_pairs.h"
 
 namespace {
 
@@ -419,6 +420,59 @@ Tensor knn_cosine_topk(const Tensor& Xn, int64_t k) {
   return nbr;
 }
 
+// the k best novel drug-disease pairs under the decoder MLP (dgmi_pairs.hip): (drug, disease, logit) of k slots each, and
+// info = [number returned, out-of-range flag].  int64 known ids are clamped into [-1, INT32_MAX] on the device, so an id
+// beyond int32 still reads as out of range; nothing here synchronises.
+std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_topk(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
+                                                         const Tensor& w3, const Tensor& b3, const OptTensor& known_drug,
+                                                         const OptTensor& known_dis, int64_t k) {
+  Dense p = dense_of(P, "P"), q = dense_of(Q, "Q");
+  TORCH_CHECK(p.F == 128 && q.F == 128, "P and Q must have 128 columns (the decoder's lin1 width), got ", p.F, " and ", q.F);
+  check(W2, at::kFloat, 2, "W2", P);
+  TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
+  check(b2, at::kFloat, 1, "b2", P);
+  check(w3, at::kFloat, 1, "w3", P);
+  check(b3, at::kFloat, 1, "b3", P);
+  TORCH_CHECK(b2.numel() == 64 && w3.numel() == 64 && b3.numel() == 1, "b2 / w3 / b3 must have 64 / 64 / 1 entries");
+  TORCH_CHECK(k >= 1 && k <= DGMI_PAIR_TOPK_MAX_K, "k must be in 1..", DGMI_PAIR_TOPK_MAX_K, ", got ", k);
+  const bool has_known = known_drug.has_value() && known_drug->defined();
+  TORCH_CHECK(has_known == (known_dis.has_value() && known_dis->defined()), "known_drug and known_dis go together");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(p.t.device());
+  Tensor kd, ks;
+  if (has_known) {
+    for (const Tensor* t : {&*known_drug, &*known_dis}) {
+      check_dev(*t, "known ids");
+      TORCH_CHECK(t->dim() == 1 && (t->scalar_type() == at::kInt || t->scalar_type() == at::kLong) && t->device() == P.device(),
+                  "known ids must be 1-D int32 / int64 tensors on ", P.device().str());
+    }
+    TORCH_CHECK(known_drug->numel() == known_dis->numel(), "known_drug / known_dis length mismatch");
+    auto i32 = [](const Tensor& t) {
+      return t.scalar_type() == at::kInt ? t.contiguous() : t.clamp(-1, (int64_t)INT32_MAX).to(at::kInt).contiguous();
+    };
+    kd = i32(*known_drug);
+    ks = i32(*known_dis);
+  }
+  const int64_t n_known = has_known ? kd.numel() : 0;
+  auto opts = p.t.options();
+  Tensor out_drug = at::empty({k}, opts.dtype(at::kInt)), out_dis = at::empty({k}, opts.dtype(at::kInt));
+  Tensor out_logit = at::empty({k}, opts.dtype(at::kFloat));
+  Tensor info = at::zeros({2}, opts.dtype(at::kInt));
+  if (p.rows == 0 || q.rows == 0) return {out_drug, out_dis, out_logit, info};
+  Tensor W2c = W2.contiguous(), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(p.t.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(q.t.data_ptr()) & 15) == 0 &&
+                  p.ld % 4 == 0 && q.ld % 4 == 0, "P and Q rows must be 16-B aligned");
+  const size_t wbytes = dgmi_pair_topk_workspace_bytes(p.rows, q.rows, (int32_t)k);
+  Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
+  check_status(dgmi_pair_mlp_topk_f32(p.t.data_ptr<float>(), p.ld, p.rows, q.t.data_ptr<float>(), q.ld, q.rows, 128, 64,
+                                      W2c.data_ptr<float>(), b2c.data_ptr<float>(), w3c.data_ptr<float>(), b3c.data_ptr<float>(),
+                                      has_known ? kd.data_ptr<int32_t>() : nullptr, has_known ? ks.data_ptr<int32_t>() : nullptr,
+                                      n_known, (int32_t)k, out_drug.data_ptr<int32_t>(), out_dis.data_ptr<int32_t>(),
+                                      out_logit.data_ptr<float>(), info.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(),
+                                      stream_of(p.t)),
+               "dgmi_pair_mlp_topk_f32");
+  return {out_drug, out_dis, out_logit, info};
+}
+
 // `like`: any tensor on the target device (the op needs a device to allocate on)
 Tensor random_subset_select(const Tensor& like, int64_t E, int64_t keep, int64_t seed, int64_t e_offset) {
   check_dev(like, "like");
@@ -619,6 +673,8 @@ TORCH_LIBRARY(dreamgnn_mi, m) {
         "float mask_scale=1., int column_passes=0, int id_mult=0) -> ()");
   m.def("epilogue_backward(Tensor dY, Tensor Y, Tensor? mask, int act, float slope, float mask_scale) -> Tensor");
   m.def("knn_cosine_topk(Tensor Xn, int k) -> Tensor");
+  m.def("pair_mlp_topk(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_drug, Tensor? known_dis, "
+        "int k) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("scale_rows(Tensor X, Tensor scale) -> Tensor");
   m.def("colsum_rows_(Tensor(a!) feat_ext, Tensor coef, int n, int R, int i0) -> ()");
   m.def("colsum_rows_backward_(Tensor(a!) gf, Tensor coef, Tensor gs, int n, int R, int i0) -> ()");
@@ -646,6 +702,7 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
   m.impl("spmm_sliced_out", spmm_sliced_out);
   m.impl("epilogue_backward", epilogue_backward);
   m.impl("knn_cosine_topk", knn_cosine_topk);
+  m.impl("pair_mlp_topk", pair_mlp_topk);
   m.impl("scale_rows", scale_rows);
   m.impl("colsum_rows_", colsum_rows_);
   m.impl("colsum_rows_backward_", colsum_rows_backward_);

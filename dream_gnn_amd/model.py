@@ -187,6 +187,22 @@ class MLPDecoder(nn.Module):
         out = _edge_linear_relu_dropout(self.lin2, self.dropout, out)
         return _edge_linear(self.lin3, out)
 
+    def top_pairs(self, drug_feat, dis_feat, k, known=None):
+        """The eval-mode decoder over ALL (drug, disease) pairs, reduced to the ``k`` best on the device
+        (``ops.pair_mlp_topk``): ``(drug_id, disease_id, logit)`` device tensors, ordered by logit descending, ties by
+        ``(drug_id, disease_id)`` ascending, NaN last; pairs in ``known = (drug_ids, disease_ids)`` are left out.
+        ``lin1`` is split as in :attr:`fuse_lin1` (two small GEMMs in torch); the rest is one HIP kernel.  Dropout is
+        not applied (eval mode).  ``1 <= k <= 1024``."""
+        k = int(k)
+        if not 1 <= k <= ops.PAIR_TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d (the on-chip top-k limit), got %d" % (ops.PAIR_TOPK_MAX_K, k))
+        Fd = drug_feat.shape[1]
+        w1 = self.lin1.weight
+        P = torch.addmm(self.lin1.bias, drug_feat, w1[:, :Fd].t())
+        Q = dis_feat @ w1[:, Fd:].t()
+        kd, ks = (None, None) if known is None else known
+        return ops.pair_mlp_topk(P, Q, self.lin2.weight, self.lin2.bias, self.lin3.weight, self.lin3.bias, kd, ks, k)
+
 
 class Net(nn.Module):
     """``TGCN[GCMCLayer x L] || FGCN -> Attention -> MLPDecoder`` — model.py:4-103.
@@ -221,6 +237,23 @@ class Net(nn.Module):
     def forward(self, enc_graph, dec_graph, drug_graph, drug_sim_feat, drug_feat, dis_graph,
                 disease_sim_feat, dis_feat, drug_feature_graph=None, disease_feature_graph=None,
                 Two_Stage=False):
+        drug_feats, dis_feats, drug_out, drug_sim_out, dis_out, dis_sim_out = self._encode(
+            enc_graph, drug_graph, drug_sim_feat, drug_feat, dis_graph, disease_sim_feat, dis_feat, drug_feature_graph,
+            disease_feature_graph, Two_Stage)
+        pred = self.decoder(dec_graph, drug_feats, dis_feats)
+        return pred, drug_out, drug_sim_out, dis_out, dis_sim_out
+
+    def embed(self, enc_graph, drug_graph, drug_sim_feat, drug_feat, dis_graph, disease_sim_feat, dis_feat,
+              drug_feature_graph=None, disease_feature_graph=None, Two_Stage=False):
+        """``forward`` without the decoder: the attention-fused ``(drug_feats, dis_feats)`` the decoder consumes
+        (model.py:236-238 of the reference's flow).  Same arguments as ``forward`` minus ``dec_graph``."""
+        drug_feats, dis_feats, *_ = self._encode(enc_graph, drug_graph, drug_sim_feat, drug_feat, dis_graph,
+                                                 disease_sim_feat, dis_feat, drug_feature_graph, disease_feature_graph,
+                                                 Two_Stage)
+        return drug_feats, dis_feats
+
+    def _encode(self, enc_graph, drug_graph, drug_sim_feat, drug_feat, dis_graph, disease_sim_feat, dis_feat,
+                drug_feature_graph, disease_feature_graph, Two_Stage):
         drug_out = dis_out = None
         for i, layer in enumerate(self.TGCN):
             drug_o, dis_o = layer(enc_graph, drug_feat, dis_feat, Two_Stage)
@@ -235,8 +268,7 @@ class Net(nn.Module):
                                                   drug_feature_graph, disease_feature_graph)
         drug_feats, _ = self.attention(torch.stack([drug_out, drug_sim_out], dim=1))
         dis_feats, _ = self.attention(torch.stack([dis_out, dis_sim_out], dim=1))
-        pred = self.decoder(dec_graph, drug_feats, dis_feats)
-        return pred, drug_out, drug_sim_out, dis_out, dis_sim_out
+        return drug_feats, dis_feats, drug_out, drug_sim_out, dis_out, dis_sim_out
 
 
 def common_loss(emb1, emb2):

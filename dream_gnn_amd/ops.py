@@ -1098,6 +1098,33 @@ def knn_cosine_topk(xn: torch.Tensor, k: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------
+# all-pairs decoder top-k — the scoring loop of train.py:26-151 without the pair list
+# ---------------------------------------------------------------------------------------------
+PAIR_TOPK_MAX_K = _lib.PAIR_TOPK_MAX_K
+
+
+def pair_mlp_topk(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                  b3: torch.Tensor, known_drug: Optional[torch.Tensor], known_dis: Optional[torch.Tensor],
+                  k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The ``min(k, #candidates)`` pairs ``(i, j)`` not in ``(known_drug, known_dis)`` with the largest
+    ``logit = b3 + w3 . relu(W2 relu(P[i] + Q[j]) + b2)`` (``dgmi_pair_mlp_topk_f32``), ordered by logit descending,
+    ties by ``(i, j)`` ascending, NaN last.  ``P`` (n_drug x 128), ``Q`` (n_dis x 128); ``W2`` (64 x 128), ``b2``,
+    ``w3`` (64), ``b3`` (1).  Returns int64 drug ids, int64 disease ids and fp32 logits on the device; the only
+    host sync is reading the count.  Raises ``ValueError`` for ``k`` outside 1..1024 and ``RuntimeError`` when a
+    known id is out of range."""
+    k = int(k)
+    if not 1 <= k <= PAIR_TOPK_MAX_K:
+        raise ValueError("k must be in 1..%d (the on-chip top-k limit), got %d" % (PAIR_TOPK_MAX_K, k))
+    _require_device(P, Q, W2, b2, w3, b3, known_drug, known_dis)
+    drug, dis, logit, info = _T.pair_mlp_topk(P, Q, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), known_drug,
+                                              known_dis, k)
+    n, bad = (int(v) for v in info.tolist())
+    if bad:
+        raise RuntimeError("pair_mlp_topk: a known (drug, disease) id is outside [0, %d) x [0, %d)"
+                           % (P.shape[0], Q.shape[0]))
+    return drug[:n].long(), dis[:n].long(), logit[:n]
+
+# ---------------------------------------------------------------------------------------------
 # (D3) edge-dropout selection — augmentation.py:48-52, 114-118
 # ---------------------------------------------------------------------------------------------
 def random_subset_select(E: int, keep: int, seed: int, device, e_offset: int = 0) -> torch.Tensor:

@@ -1,0 +1,109 @@
+"""The model's deliverable: the most likely NEW drug-disease associations of a trained ``Net``.
+
+Counterpart of the reference's ``get_top_novel_predictions`` (train.py:26-151, called per fold at :370-376 with
+``--top_k``, default 200).  The reference lists every pair absent from the association matrix in Python, re-runs the
+whole model (encoder included) on decoder graphs of 5 000 of them at a time, applies ``sigmoid`` and sorts the scores
+with pandas.  Here the encoder runs once (``Net.embed``), the decoder's first layer is split into two small GEMMs, and
+one HIP kernel scores every pair and keeps the k best on the device (``MLPDecoder.top_pairs``,
+``csrc/dgmi_pairs.hip``).
+
+Ranking uses the fp32 LOGIT, not the fp32 sigmoid: in fp32 the sigmoid rounds to exactly 1.0 above a logit of about
+17, and the reference's sort leaves the order among equal scores unspecified.  Here the order is the logit
+descending, ties broken by ``(drug_id, disease_id)`` ascending (the reference's drug-major enumeration order), NaN
+logits last.  Wherever the reference's own scores are distinct, the two orders agree.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import ops
+
+#: the largest ``k`` the on-chip top-k takes; there is no other path
+MAX_K = ops.PAIR_TOPK_MAX_K
+
+
+@dataclass
+class NovelPairs:
+    """The ranked pairs, CPU tensors in rank order: int64 ``drug_id`` / ``disease_id``, fp32 ``logit`` and
+    ``score = sigmoid(logit)``."""
+
+    drug_id: torch.Tensor
+    disease_id: torch.Tensor
+    logit: torch.Tensor
+    score: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.drug_id.numel())
+
+    def to_frame(self, drug_names=None):
+        """A pandas DataFrame with the reference's columns (train.py:129-141): ``drug_id, disease_id, score`` and,
+        when ``drug_names`` (indexable by drug id) is given, ``drug_name``."""
+        import pandas as pd
+
+        df = pd.DataFrame({"drug_id": self.drug_id.numpy(), "disease_id": self.disease_id.numpy(),
+                           "score": self.score.numpy()})
+        if drug_names is not None:
+            names = list(drug_names)
+            df["drug_name"] = [names[i] for i in df["drug_id"]]
+        return df
+
+
+def _known_ids(known, n_drug: int, n_dis: int, device):
+    """``known`` as (drug_ids, disease_ids) device tensors, or (None, None) when nothing is known."""
+    if known is None:
+        return None, None
+    if isinstance(known, (tuple, list)):
+        if len(known) != 2:
+            raise ValueError("known must be an (n_drug, n_dis) matrix or a (drug_ids, disease_ids) pair")
+        kd, ks = (torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).reshape(-1) for x in known)
+        if kd.numel() != ks.numel():
+            raise ValueError("known drug / disease id lists differ in length: %d vs %d" % (kd.numel(), ks.numel()))
+        if kd.is_floating_point() or ks.is_floating_point():
+            raise ValueError("known ids must be integers")
+    else:
+        shape = tuple(known.shape)
+        if shape != (n_drug, n_dis):
+            raise ValueError("known matrix has shape %s, expected (n_drug, n_dis) = (%d, %d)" % (shape, n_drug, n_dis))
+        if isinstance(known, torch.Tensor):
+            kd, ks = (known != 0).nonzero(as_tuple=True)  # NaN != 0: a NaN cell counts as known, as in train.py:55
+        else:
+            kd, ks = (torch.from_numpy(x) for x in np.nonzero(np.asarray(known) != 0))
+    if kd.numel() == 0:
+        return None, None
+    return kd.to(device=device, dtype=torch.int64), ks.to(device=device, dtype=torch.int64)
+
+
+def top_novel_pairs(net, batch, known, k: int = 200) -> NovelPairs:
+    """The ``min(k, #novel)`` pairs not in ``known`` that ``net`` scores highest, eval mode.
+
+    ``batch``: one fold's un-augmented inputs (the dict of ``harness``: ``enc_graph``, ``drug_graph``,
+    ``drug_sim_feat``, ``drug_feat``, ``disease_graph``, ``disease_sim_feat``, ``disease_feat`` and the optional
+    ``drug_feature_graph`` / ``disease_feature_graph``).  ``known``: the association matrix (n_drug x n_dis, numpy or
+    torch, nonzero = known; every known association of the dataset, as train.py:46 uses) or a
+    ``(drug_ids, disease_ids)`` pair.  ``1 <= k <= 1024``; larger ``k`` raises ``ValueError``.
+
+    The encoder runs once under ``no_grad``; the net's training flag is restored afterwards.  Ordered by logit
+    descending, ties by ``(drug_id, disease_id)`` ascending, NaN last (module docstring: why the logit and not the
+    sigmoid)."""
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k must be in 1..%d (the on-chip top-k limit), got %d" % (MAX_K, k))
+    n_drug, n_dis = int(batch["drug_feat"].shape[0]), int(batch["disease_feat"].shape[0])
+    device = batch["drug_feat"].device
+    kd, ks = _known_ids(known, n_drug, n_dis, device)
+
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            hd, hs = net.embed(batch["enc_graph"], batch["drug_graph"], batch["drug_sim_feat"], batch["drug_feat"],
+                               batch["disease_graph"], batch["disease_sim_feat"], batch["disease_feat"],
+                               batch.get("drug_feature_graph"), batch.get("disease_feature_graph"))
+            drug, dis, logit = net.decoder.top_pairs(hd, hs, k, None if kd is None else (kd, ks))
+    finally:
+        net.train(was_training)
+    logit = logit.cpu()
+    return NovelPairs(drug.cpu(), dis.cpu(), logit, torch.sigmoid(logit))
