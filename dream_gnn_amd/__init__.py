@@ -15,7 +15,8 @@ The package holds only what the path needs:
   path can be driven end to end without DGL or the reference;
 * ``synth``    — device-side generators for the synthetic configs;
 * ``shard``    — nnz-balanced edge partition + RCCL exchange for the multi-GPU configs;
-* ``predict``  — ``top_novel_pairs``: the k best novel drug-disease pairs of a trained ``Net`` (train.py:26-151).
+* ``predict``  — ``top_novel_pairs``: the k best novel drug-disease pairs of a trained ``Net`` (train.py:26-151);
+  ``top_novel_per_disease`` / ``top_novel_per_drug``: the k best novel candidates of every disease / drug.
 
 There is no CPU fallback: every op raises if ``libdgmi.so`` is missing or a tensor is
 not on a HIP device.
@@ -23,7 +24,8 @@ not on a HIP device.
 from . import _lib  # noqa: F401  (fails loudly if the extension is not built)
 from .ops import (CSRGraph, EdgePairs, SlicedCSR, SpmmPlan, csr_from_coo, gather_add, gather_concat,  # noqa: F401
                   random_subset_mask, spmm_csr)
-from .predict import NovelPairs, top_novel_pairs  # noqa: F401
+from .predict import NovelLists, NovelPairs, top_novel_pairs, top_novel_per_disease, top_novel_per_drug  # noqa: F401
 
 __all__ = ["CSRGraph", "EdgePairs", "SlicedCSR", "SpmmPlan", "csr_from_coo", "gather_add", "gather_concat",
-           "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs"]
+           "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs", "NovelLists", "top_novel_per_disease",
+           "top_novel_per_drug"]

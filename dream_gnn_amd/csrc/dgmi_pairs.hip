@@ -13,6 +13,7 @@
 // (Q: per task), P rows come from LDS as a two-address broadcast.  Two drugs x two row halves = 4 independent
 // accumulators per wave, the condition for the 64-cycle f32 MFMA to issue back to back from one wave per SIMD.
 // After the 64 steps each lane sums w3[h] relu(acc + b2[h]) over its 32 rows and adds its partner lane (l ^ 32).
+// The scorer lives in dgmi_pair_score.h, shared with the per-row top-k (dgmi_pairs_rows.hip): same logits, same bits.
 //
 // Top-k.  A persistent grid of one workgroup per CU takes (drug chunk, 128-disease group) tasks in drug-major order,
 // so all workgroups read the same P rows at the same time.  Each keeps, in LDS, its best-k list followed by an append
@@ -25,12 +26,11 @@
 #include <stdint.h>
 
 #include "dgmi.h"
+#include "dgmi_pair_score.h"
 #include "dgmi_pairs.h"
 
 namespace {
 
-constexpr int kH1 = 128;                 // decoder hidden width 1 (layers.py:349)
-constexpr int kH2 = 64;                  // decoder hidden width 2 (layers.py:350)
 constexpr int kThreads = 256;            // 4 waves; each owns 32 diseases of the task's group
 constexpr int kGroupCols = 128;          // diseases per task
 constexpr int kMaxChunk = 64;            // drugs per task (at most)
@@ -43,28 +43,10 @@ constexpr int kMergeCap = 8192;          // entries one merge workgroup sorts
 constexpr int kMaxFan = 64;
 constexpr size_t kAlign = 256;
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-// order-preserving key of a logit: larger logit -> larger key; NaN -> 0, below every number; -0 == +0
-__device__ __forceinline__ uint32_t order_key(float x) {
-  if (x != x) return 0u;
-  uint32_t u = __float_as_uint(x);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_logit(uint32_t f) {
-  if (f == 0u) return __uint_as_float(0x7fc00000u);
-  return __uint_as_float((f & 0x80000000u) ? (f & 0x7fffffffu) : ~f);
-}
-
 // the full ranking key: logit descending, then drug ascending, then disease ascending
 __device__ __forceinline__ bool better(uint32_t fa, uint32_t ia, uint32_t ja, uint32_t fb, uint32_t ib, uint32_t jb) {
   return fa > fb || (fa == fb && (ia < ib || (ia == ib && ja < jb)));
 }
-
-// relu that keeps NaN (torch.relu does; fmaxf would drop it)
-__device__ __forceinline__ float relu_nan(float x) { return x < 0.f ? 0.f : x; }
 
 // Bitonic sort of n (a power of two) entries of the SoA list (f, i, j) into descending key order, all threads of the
 // block.  Ends with a barrier.
@@ -95,20 +77,6 @@ __device__ __forceinline__ void set_pad(uint32_t* f, uint32_t* ii, uint32_t* jj,
   jj[e] = 0xffffffffu;
 }
 
-// known[(i, j)] -> bit j & 31 of word i * nwords + j / 32; an id outside its range sets info[1]
-__global__ __launch_bounds__(256) void known_bitmap_kernel(const int32_t* __restrict__ kd, const int32_t* __restrict__ ks,
-                                                           int64_t n_known, int n_drug, int n_dis, int64_t nwords,
-                                                           uint32_t* __restrict__ bitmap, int32_t* __restrict__ info) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_known; e += (int64_t)gridDim.x * 256) {
-    const int32_t i = kd[e], j = ks[e];
-    if (i < 0 || i >= n_drug || j < 0 || j >= n_dis) {
-      atomicOr(&info[1], 1);
-      continue;
-    }
-    atomicOr(&bitmap[(int64_t)i * nwords + (j >> 5)], 1u << (j & 31));
-  }
-}
-
 struct ScoreArgs {
   const float* P;
   int64_t ldp;
@@ -137,25 +105,8 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
   const int half = lane >> 5, col = lane & 31;
   const int k = a.k;
 
-  // this lane's W2 operands (rows col and 32 + col, k = 64 half + s) and epilogue rows h = 32 hb + 8 (r >> 2) + 4 half + (r & 3)
-  float wa[kH1 / 2], wb[kH1 / 2];
-#pragma unroll
-  for (int s4 = 0; s4 < 16; ++s4) {
-    const float4 x = *reinterpret_cast<const float4*>(a.W2 + col * kH1 + 64 * half + 4 * s4);
-    const float4 y = *reinterpret_cast<const float4*>(a.W2 + (32 + col) * kH1 + 64 * half + 4 * s4);
-    wa[4 * s4] = x.x, wa[4 * s4 + 1] = x.y, wa[4 * s4 + 2] = x.z, wa[4 * s4 + 3] = x.w;
-    wb[4 * s4] = y.x, wb[4 * s4 + 1] = y.y, wb[4 * s4 + 2] = y.z, wb[4 * s4 + 3] = y.w;
-  }
-  float eb[2][16], ew[2][16];
-#pragma unroll
-  for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int h = 32 * hb + 8 * (r >> 2) + 4 * half + (r & 3);
-      eb[hb][r] = a.b2[h];
-      ew[hb][r] = a.w3[h];
-    }
-  const float bias3 = a.b3[0];
+  PairDecoder dec;  // this lane's W2 operands and epilogue constants
+  load_decoder(dec, a.W2, a.b2, a.w3, a.b3, half, col);
 
   if (tid == 0) s_used = 0;
   bool full = false;  // the list holds k entries: (tf, ti, tj) is its k-th key
@@ -218,11 +169,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
     const bool col_ok = j < a.n_dis;
     const int jc = col_ok ? j : a.n_dis - 1;
     float q[kH1 / 2];
-#pragma unroll
-    for (int s4 = 0; s4 < 16; ++s4) {
-      const float4 x = *reinterpret_cast<const float4*>(a.Q + (int64_t)jc * a.ldq + 64 * half + 4 * s4);
-      q[4 * s4] = x.x, q[4 * s4 + 1] = x.y, q[4 * s4 + 2] = x.z, q[4 * s4 + 3] = x.w;
-    }
+    load_lane_row(q, a.Q + (int64_t)jc * a.ldq, half);
     const bool words = a.bitmap != nullptr && j0 < a.n_dis;
     const uint32_t* bm = a.bitmap + (words ? (j0 >> 5) : 0);
     __syncthreads();
@@ -236,38 +183,8 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
         const uint32_t kwb = words ? bm[(int64_t)(i0 + db) * a.nwords] : 0u;
         const float* pa = p_lds + da * kPStride + 68 * half;
         const float* pb = p_lds + db * kPStride + 68 * half;
-        floatx16 c00, c01, c10, c11;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) c00[v] = c01[v] = c10[v] = c11[v] = 0.f;
-#pragma unroll
-        for (int s4 = 0; s4 < 16; ++s4) {
-          const float4 xa = *reinterpret_cast<const float4*>(pa + 4 * s4);
-          const float4 xb = *reinterpret_cast<const float4*>(pb + 4 * s4);
-          const float va[4] = {xa.x, xa.y, xa.z, xa.w}, vb[4] = {xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int s = 4 * s4 + u;
-            const float ba = relu_nan(va[u] + q[s]);
-            const float bb = relu_nan(vb[u] + q[s]);
-            c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s], ba, c00, 0, 0, 0);
-            c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[s], ba, c01, 0, 0, 0);
-            c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[s], bb, c10, 0, 0, 0);
-            c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[s], bb, c11, 0, 0, 0);
-          }
-        }
-        float sa = 0.f, sb = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sa = fmaf(ew[0][r], relu_nan(c00[r] + eb[0][r]), sa);
-          sb = fmaf(ew[0][r], relu_nan(c10[r] + eb[0][r]), sb);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sa = fmaf(ew[1][r], relu_nan(c01[r] + eb[1][r]), sa);
-          sb = fmaf(ew[1][r], relu_nan(c11[r] + eb[1][r]), sb);
-        }
-        const float la = (sa + __shfl_xor(sa, 32)) + bias3;
-        const float lb = (sb + __shfl_xor(sb, 32)) + bias3;
+        float la, lb;
+        score_two(pa, pb, q, dec, la, lb);
         offer(col_ok && !((kwa >> col) & 1u), la, (uint32_t)(i0 + da), (uint32_t)j);
         offer(has_b && col_ok && !((kwb >> col) & 1u), lb, (uint32_t)(i0 + db), (uint32_t)j);
       }

@@ -26,6 +26,7 @@
 
 #include "dgmi.h"
 #include "dgmi_pairs.h"
+#include "dgmi_rank.h"
 
 namespace {
 
@@ -473,6 +474,62 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_topk(const Tensor& P, const 
   return {out_drug, out_dis, out_logit, info};
 }
 
+// the k best novel candidates of every query row under the decoder MLP (dgmi_pairs_rows.hip): candidate ids and logits
+// (n_query x k, padded with -1 / NaN), per-row counts and info = [sum of counts, out-of-range flag].  X is the query side
+// (Q for per-disease lists, P for per-drug lists), C the candidate side.  int64 known ids are clamped into
+// [-1, INT32_MAX] on the device, as in pair_mlp_topk; nothing here synchronises.
+std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_row_topk(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2,
+                                                             const Tensor& w3, const Tensor& b3, const OptTensor& known_query,
+                                                             const OptTensor& known_cand, int64_t k) {
+  Dense x = dense_of(X, "X"), c = dense_of(C, "C");
+  TORCH_CHECK(x.F == 128 && c.F == 128, "X and C must have 128 columns (the decoder's lin1 width), got ", x.F, " and ", c.F);
+  check(W2, at::kFloat, 2, "W2", X);
+  TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
+  check(b2, at::kFloat, 1, "b2", X);
+  check(w3, at::kFloat, 1, "w3", X);
+  check(b3, at::kFloat, 1, "b3", X);
+  TORCH_CHECK(b2.numel() == 64 && w3.numel() == 64 && b3.numel() == 1, "b2 / w3 / b3 must have 64 / 64 / 1 entries");
+  TORCH_CHECK(k >= 1 && k <= DGMI_ROW_TOPK_MAX_K, "k must be in 1..", DGMI_ROW_TOPK_MAX_K, ", got ", k);
+  const bool has_known = known_query.has_value() && known_query->defined();
+  TORCH_CHECK(has_known == (known_cand.has_value() && known_cand->defined()), "known_query and known_cand go together");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.t.device());
+  Tensor kq, kc;
+  if (has_known) {
+    for (const Tensor* t : {&*known_query, &*known_cand}) {
+      check_dev(*t, "known ids");
+      TORCH_CHECK(t->dim() == 1 && (t->scalar_type() == at::kInt || t->scalar_type() == at::kLong) && t->device() == X.device(),
+                  "known ids must be 1-D int32 / int64 tensors on ", X.device().str());
+    }
+    TORCH_CHECK(known_query->numel() == known_cand->numel(), "known_query / known_cand length mismatch");
+    auto i32 = [](const Tensor& t) {
+      return t.scalar_type() == at::kInt ? t.contiguous() : t.clamp(-1, (int64_t)INT32_MAX).to(at::kInt).contiguous();
+    };
+    kq = i32(*known_query);
+    kc = i32(*known_cand);
+  }
+  const int64_t n_known = has_known ? kq.numel() : 0;
+  auto opts = x.t.options();
+  Tensor out_cand = at::empty({x.rows, k}, opts.dtype(at::kInt));
+  Tensor out_logit = at::empty({x.rows, k}, opts.dtype(at::kFloat));
+  Tensor out_count = at::empty({x.rows}, opts.dtype(at::kInt));
+  Tensor info = at::zeros({2}, opts.dtype(at::kInt));
+  if (x.rows == 0) return {out_cand, out_logit, out_count, info};
+  Tensor W2c = W2.contiguous(), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.t.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(c.t.data_ptr()) & 15) == 0 &&
+                  x.ld % 4 == 0 && c.ld % 4 == 0, "X and C rows must be 16-B aligned");
+  // per call, from the caching allocator, as pair_mlp_topk
+  const size_t wbytes = dgmi_row_topk_workspace_bytes(x.rows, c.rows, (int32_t)k);
+  Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
+  check_status(dgmi_pair_mlp_row_topk_f32(x.t.data_ptr<float>(), x.ld, x.rows, c.t.data_ptr<float>(), c.ld, c.rows, 128, 64,
+                                          W2c.data_ptr<float>(), b2c.data_ptr<float>(), w3c.data_ptr<float>(), b3c.data_ptr<float>(),
+                                          has_known ? kq.data_ptr<int32_t>() : nullptr, has_known ? kc.data_ptr<int32_t>() : nullptr,
+                                          n_known, (int32_t)k, out_cand.data_ptr<int32_t>(), out_logit.data_ptr<float>(),
+                                          out_count.data_ptr<int32_t>(), info.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(),
+                                          stream_of(x.t)),
+               "dgmi_pair_mlp_row_topk_f32");
+  return {out_cand, out_logit, out_count, info};
+}
+
 // `like`: any tensor on the target device (the op needs a device to allocate on)
 Tensor random_subset_select(const Tensor& like, int64_t E, int64_t keep, int64_t seed, int64_t e_offset) {
   check_dev(like, "like");
@@ -675,6 +732,8 @@ TORCH_LIBRARY(dreamgnn_mi, m) {
   m.def("knn_cosine_topk(Tensor Xn, int k) -> Tensor");
   m.def("pair_mlp_topk(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_drug, Tensor? known_dis, "
         "int k) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("pair_mlp_row_topk(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_query, "
+        "Tensor? known_cand, int k) -> (Tensor cand, Tensor logit, Tensor count, Tensor info)");
   m.def("scale_rows(Tensor X, Tensor scale) -> Tensor");
   m.def("colsum_rows_(Tensor(a!) feat_ext, Tensor coef, int n, int R, int i0) -> ()");
   m.def("colsum_rows_backward_(Tensor(a!) gf, Tensor coef, Tensor gs, int n, int R, int i0) -> ()");
@@ -703,6 +762,7 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
   m.impl("epilogue_backward", epilogue_backward);
   m.impl("knn_cosine_topk", knn_cosine_topk);
   m.impl("pair_mlp_topk", pair_mlp_topk);
+  m.impl("pair_mlp_row_topk", pair_mlp_row_topk);
   m.impl("scale_rows", scale_rows);
   m.impl("colsum_rows_", colsum_rows_);
   m.impl("colsum_rows_backward_", colsum_rows_backward_);

@@ -9,6 +9,7 @@ order, same residual accumulation ``out += layer_out / (i + 1)`` (model.py:69-74
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -202,6 +203,73 @@ class MLPDecoder(nn.Module):
         Q = dis_feat @ w1[:, Fd:].t()
         kd, ks = (None, None) if known is None else known
         return ops.pair_mlp_topk(P, Q, self.lin2.weight, self.lin2.bias, self.lin3.weight, self.lin3.bias, kd, ks, k)
+
+    def top_pairs_per_row(self, drug_feat, dis_feat, k, by="disease", known=None, rows=None):
+        """The eval-mode decoder over ALL (drug, disease) pairs, reduced to the ``k`` best candidates of every query row
+        on the device (``ops.pair_mlp_row_topk``).  ``by="disease"``: the queries are diseases and the candidates drugs
+        (which drugs fit disease X); ``by="drug"``: the queries are drugs and the candidates diseases.  Pairs in
+        ``known = (drug_ids, disease_ids)`` are left out.  ``rows``: an optional 1-D subset of query ids (unique, in
+        range); only those rows are scored.  ``lin1`` is split as in :meth:`top_pairs`, and every logit is bit-identical
+        to the one :meth:`top_pairs` computes for the same pair.  ``1 <= k <= 128``.
+
+        Returns ``(query_id, cand_id, logit, count)`` device tensors: int64 ``query_id`` (n_q), int64 ``cand_id`` and
+        fp32 ``logit`` (n_q x k, ordered by logit descending, ties by candidate id ascending, NaN last; -1 / NaN past
+        the row's count) and int32 ``count`` (n_q)."""
+        k = int(k)
+        if not 1 <= k <= ops.ROW_TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d (the per-row on-chip top-k limit), got %d" % (ops.ROW_TOPK_MAX_K, k))
+        if by not in ("disease", "drug"):
+            raise ValueError('by must be "disease" or "drug", got %r' % (by,))
+        n_query = int(dis_feat.shape[0] if by == "disease" else drug_feat.shape[0])
+        sub = query_rows(rows, n_query)
+        Fd = drug_feat.shape[1]
+        w1 = self.lin1.weight
+        P = torch.addmm(self.lin1.bias, drug_feat, w1[:, :Fd].t())
+        Q = dis_feat @ w1[:, Fd:].t()
+        X, C = (Q, P) if by == "disease" else (P, Q)
+        kq = kc = None
+        if known is not None:
+            kd, ks = known
+            kq, kc = (ks, kd) if by == "disease" else (kd, ks)
+        if sub is None:
+            query_id = torch.arange(n_query, device=X.device)
+        else:
+            query_id = sub.to(X.device)
+            X = X.index_select(0, query_id)
+            if kq is not None:
+                kq, kc = _remap_known(kq.to(X.device).long(), kc.to(X.device).long(), query_id, n_query, C.shape[0])
+        cand, logit, count = ops.pair_mlp_row_topk(X, C, self.lin2.weight, self.lin2.bias, self.lin3.weight,
+                                                   self.lin3.bias, kq, kc, k)
+        return query_id, cand, logit, count
+
+
+def query_rows(rows, n_query: int):
+    """``rows`` as a CPU int64 tensor of unique query ids in ``[0, n_query)``, or None; ``ValueError`` otherwise."""
+    if rows is None:
+        return None
+    r = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows))
+    if r.dim() != 1 or r.is_floating_point() or r.is_complex() or r.dtype == torch.bool:
+        raise ValueError("rows must be a 1-D list of integer query ids, got %s of shape %s" % (r.dtype, tuple(r.shape)))
+    r = r.detach().cpu().long()
+    if r.numel() and (int(r.min()) < 0 or int(r.max()) >= n_query):
+        raise ValueError("rows holds a query id outside [0, %d)" % n_query)
+    if torch.unique(r).numel() != r.numel():
+        raise ValueError("rows holds a duplicate query id")
+    return r
+
+
+def _remap_known(kq, kc, rows, n_query, n_cand):
+    """The known pairs of the query subset ``rows``, with query ids renumbered to positions in ``rows``.  A pair with an
+    id outside ``[0, n_query) x [0, n_cand)`` is kept with query -1, so that the kernel still flags it."""
+    if n_query == 0:
+        return kq, kc
+    pos = torch.full((n_query,), -1, dtype=torch.long, device=rows.device)
+    pos[rows] = torch.arange(rows.numel(), device=rows.device)
+    q_ok = (kq >= 0) & (kq < n_query)
+    c_ok = (kc >= 0) & (kc < n_cand)
+    q_new = torch.where(q_ok, pos[kq.clamp(0, n_query - 1)], torch.full_like(kq, -1))
+    keep = (q_new >= 0) | ~q_ok | ~c_ok
+    return q_new[keep], kc[keep]
 
 
 class Net(nn.Module):

@@ -1124,6 +1124,32 @@ def pair_mlp_topk(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.
                            % (P.shape[0], Q.shape[0]))
     return drug[:n].long(), dis[:n].long(), logit[:n]
 
+
+ROW_TOPK_MAX_K = _lib.ROW_TOPK_MAX_K
+
+
+def pair_mlp_row_topk(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                      b3: torch.Tensor, known_query: Optional[torch.Tensor], known_cand: Optional[torch.Tensor],
+                      k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """For every query row ``q`` of ``X``, the ``min(k, #candidates of q)`` rows ``c`` of ``C`` with ``(q, c)`` not in
+    ``(known_query, known_cand)`` and the largest ``logit = b3 + w3 . relu(W2 relu(X[q] + C[c]) + b2)``
+    (``dgmi_pair_mlp_row_topk_f32``), ordered by logit descending, ties by ``c`` ascending, NaN last.  Per-disease lists
+    take ``X = Q``, ``C = P``; per-drug lists ``X = P``, ``C = Q``; every logit is bit-identical to
+    :func:`pair_mlp_topk`'s for the same pair.  Returns int64 candidate ids ``(n_query, k)`` (-1 past a row's count), fp32
+    logits ``(n_query, k)`` (NaN past the count) and int32 counts ``(n_query,)`` on the device; the only host sync is
+    reading the flag.  Raises ``ValueError`` for ``k`` outside 1..128 and ``RuntimeError`` when a known id is out of
+    range."""
+    k = int(k)
+    if not 1 <= k <= ROW_TOPK_MAX_K:
+        raise ValueError("k must be in 1..%d (the per-row on-chip top-k limit), got %d" % (ROW_TOPK_MAX_K, k))
+    _require_device(X, C, W2, b2, w3, b3, known_query, known_cand)
+    cand, logit, count, info = _T.pair_mlp_row_topk(X, C, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), known_query,
+                                                    known_cand, k)
+    if int(info[1]):
+        raise RuntimeError("pair_mlp_row_topk: a known (query, candidate) id is outside [0, %d) x [0, %d)"
+                           % (X.shape[0], C.shape[0]))
+    return cand.long(), logit, count
+
 # ---------------------------------------------------------------------------------------------
 # (D3) edge-dropout selection — augmentation.py:48-52, 114-118
 # ---------------------------------------------------------------------------------------------

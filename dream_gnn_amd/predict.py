@@ -11,6 +11,11 @@ Ranking uses the fp32 LOGIT, not the fp32 sigmoid: in fp32 the sigmoid rounds to
 17, and the reference's sort leaves the order among equal scores unspecified.  Here the order is the logit
 descending, ties broken by ``(drug_id, disease_id)`` ascending (the reference's drug-major enumeration order), NaN
 logits last.  Wherever the reference's own scores are distinct, the two orders agree.
+
+``top_novel_per_disease`` / ``top_novel_per_drug`` answer the per-entity questions (which drugs fit disease X, which
+new indications fit drug Y): the k best novel candidates of every query row, from one HIP kernel over the same scorer
+(``MLPDecoder.top_pairs_per_row``, ``csrc/dgmi_pairs_rows.hip``).  Within a row the order is the global one restricted
+to that row: logit descending, ties by candidate id ascending, NaN last.
 """
 from __future__ import annotations
 
@@ -20,9 +25,12 @@ import numpy as np
 import torch
 
 from . import ops
+from .model import query_rows
 
 #: the largest ``k`` the on-chip top-k takes; there is no other path
 MAX_K = ops.PAIR_TOPK_MAX_K
+#: the largest ``k`` per row of the per-disease / per-drug lists
+ROW_MAX_K = ops.ROW_TOPK_MAX_K
 
 
 @dataclass
@@ -107,3 +115,81 @@ def top_novel_pairs(net, batch, known, k: int = 200) -> NovelPairs:
         net.train(was_training)
     logit = logit.cpu()
     return NovelPairs(drug.cpu(), dis.cpu(), logit, torch.sigmoid(logit))
+
+
+@dataclass
+class NovelLists:
+    """Per-row rankings, CPU tensors: ``by`` (``"disease"`` or ``"drug"``, the query side), int64 ``query_id`` (n_q),
+    int64 ``drug_id`` / ``disease_id`` (n_q x k, -1 past a row's count), fp32 ``logit`` and ``score = sigmoid(logit)``
+    (n_q x k, NaN past the count) and int64 ``count`` (n_q).  Row r ranks the candidates of query ``query_id[r]``."""
+
+    by: str
+    query_id: torch.Tensor
+    drug_id: torch.Tensor
+    disease_id: torch.Tensor
+    logit: torch.Tensor
+    score: torch.Tensor
+    count: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.query_id.numel())
+
+    def to_frame(self, drug_names=None):
+        """A pandas DataFrame in long form, one line per returned entry (padding left out), rows in order and each
+        row's entries by rank: ``query_id, rank, drug_id, disease_id, score`` (rank 1 is the best) and, when
+        ``drug_names`` (indexable by drug id) is given, ``drug_name``."""
+        import pandas as pd
+
+        k = int(self.drug_id.shape[1]) if self.drug_id.dim() == 2 else 0
+        valid = (torch.arange(k)[None, :] < self.count[:, None]).reshape(-1).numpy()
+        rank = np.tile(np.arange(1, k + 1), len(self))
+        qid = np.repeat(self.query_id.numpy(), k)
+        df = pd.DataFrame({"query_id": qid[valid], "rank": rank[valid],
+                           "drug_id": self.drug_id.reshape(-1).numpy()[valid],
+                           "disease_id": self.disease_id.reshape(-1).numpy()[valid],
+                           "score": self.score.reshape(-1).numpy()[valid]})
+        if drug_names is not None:
+            names = list(drug_names)
+            df["drug_name"] = [names[i] for i in df["drug_id"]]
+        return df
+
+
+def _top_novel_lists(net, batch, known, k, by, rows) -> NovelLists:
+    k = int(k)
+    if not 1 <= k <= ROW_MAX_K:
+        raise ValueError("k must be in 1..%d (the per-row on-chip top-k limit), got %d" % (ROW_MAX_K, k))
+    n_drug, n_dis = int(batch["drug_feat"].shape[0]), int(batch["disease_feat"].shape[0])
+    device = batch["drug_feat"].device
+    kd, ks = _known_ids(known, n_drug, n_dis, device)
+    rows = query_rows(rows, n_dis if by == "disease" else n_drug)
+
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            hd, hs = net.embed(batch["enc_graph"], batch["drug_graph"], batch["drug_sim_feat"], batch["drug_feat"],
+                               batch["disease_graph"], batch["disease_sim_feat"], batch["disease_feat"],
+                               batch.get("drug_feature_graph"), batch.get("disease_feature_graph"))
+            qid, cand, logit, count = net.decoder.top_pairs_per_row(hd, hs, k, by, None if kd is None else (kd, ks), rows)
+    finally:
+        net.train(was_training)
+    qid, cand, logit, count = qid.cpu(), cand.cpu(), logit.cpu(), count.cpu().long()
+    qmat = torch.where(cand >= 0, qid[:, None].expand_as(cand), torch.full_like(cand, -1))
+    drug, dis = (cand, qmat) if by == "disease" else (qmat, cand)
+    return NovelLists(by, qid, drug, dis, logit, torch.sigmoid(logit), count)
+
+
+def top_novel_per_disease(net, batch, known, k: int = 10, diseases=None) -> NovelLists:
+    """For every disease (or the diseases in ``diseases``, unique ids, in that order), the ``min(k, #novel)`` drugs not
+    known to treat it that ``net`` scores highest, eval mode: the case-study table.  ``batch`` and ``known`` as in
+    :func:`top_novel_pairs`; ``1 <= k <= 128``.  Validates ``k``, ``known`` and ``diseases`` before the model runs; the
+    encoder runs once under ``no_grad`` and the training flag is restored.  Each row is ordered by logit descending,
+    ties by drug id ascending, NaN last."""
+    return _top_novel_lists(net, batch, known, k, "disease", diseases)
+
+
+def top_novel_per_drug(net, batch, known, k: int = 10, drugs=None) -> NovelLists:
+    """For every drug (or the drugs in ``drugs``), the ``min(k, #novel)`` diseases it is not known to treat that
+    ``net`` scores highest: its best new indications.  Otherwise as :func:`top_novel_per_disease`; ties by disease id
+    ascending."""
+    return _top_novel_lists(net, batch, known, k, "drug", drugs)
