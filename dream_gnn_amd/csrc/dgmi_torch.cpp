@@ -143,6 +143,27 @@ Dense dense_of(const Tensor& X, const char* name) {
   return {t, t.size(0), F, t.size(0) > 1 ? t.stride(0) : (F > 0 ? F : 1)};
 }
 
+inline bool rows_16b_aligned(const Tensor& t, int64_t ld) {
+  return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0 && ld % 4 == 0;
+}
+
+// dense_of for the kernels that read rows as float4 (the pair rankings): a view whose rows do not start on 16-B
+// boundaries (X[:, 1:129] of a wider tensor, an odd leading dimension) is copied, as a column-strided one is
+Dense dense16_of(const Tensor& X, const char* name) {
+  Dense d = dense_of(X, name);
+  if (!rows_16b_aligned(d.t, d.ld)) {
+    d.t = d.t.clone(at::MemoryFormat::Contiguous);
+    d.ld = d.F > 0 ? d.F : 1;
+  }
+  return d;
+}
+
+// a contiguous copy-or-alias of a parameter that starts on a 16-B boundary
+Tensor contiguous16(const Tensor& t) {
+  Tensor c = t.contiguous();
+  return (reinterpret_cast<uintptr_t>(c.data_ptr()) & 15) == 0 ? c : c.clone(at::MemoryFormat::Contiguous);
+}
+
 Tensor out_of(const OptTensor& out, int64_t rows, int64_t F, const Tensor& like) {
   if (out.has_value() && out->defined()) {
     TORCH_CHECK(out->scalar_type() == at::kFloat && out->dim() == 2 && out->size(0) == rows && out->size(1) == F &&
@@ -427,7 +448,7 @@ Tensor knn_cosine_topk(const Tensor& Xn, int64_t k) {
 std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_topk(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2,
                                                          const Tensor& w3, const Tensor& b3, const OptTensor& known_drug,
                                                          const OptTensor& known_dis, int64_t k) {
-  Dense p = dense_of(P, "P"), q = dense_of(Q, "Q");
+  Dense p = dense16_of(P, "P"), q = dense16_of(Q, "Q");
   TORCH_CHECK(p.F == 128 && q.F == 128, "P and Q must have 128 columns (the decoder's lin1 width), got ", p.F, " and ", q.F);
   check(W2, at::kFloat, 2, "W2", P);
   TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
@@ -459,9 +480,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_topk(const Tensor& P, const 
   Tensor out_logit = at::empty({k}, opts.dtype(at::kFloat));
   Tensor info = at::zeros({2}, opts.dtype(at::kInt));
   if (p.rows == 0 || q.rows == 0) return {out_drug, out_dis, out_logit, info};
-  Tensor W2c = W2.contiguous(), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(p.t.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(q.t.data_ptr()) & 15) == 0 &&
-                  p.ld % 4 == 0 && q.ld % 4 == 0, "P and Q rows must be 16-B aligned");
+  Tensor W2c = contiguous16(W2), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK(rows_16b_aligned(p.t, p.ld) && rows_16b_aligned(q.t, q.ld), "P and Q rows must be 16-B aligned");
   const size_t wbytes = dgmi_pair_topk_workspace_bytes(p.rows, q.rows, (int32_t)k);
   Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
   check_status(dgmi_pair_mlp_topk_f32(p.t.data_ptr<float>(), p.ld, p.rows, q.t.data_ptr<float>(), q.ld, q.rows, 128, 64,
@@ -481,7 +501,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_topk(const Tensor& P, const 
 std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_row_topk(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2,
                                                              const Tensor& w3, const Tensor& b3, const OptTensor& known_query,
                                                              const OptTensor& known_cand, int64_t k) {
-  Dense x = dense_of(X, "X"), c = dense_of(C, "C");
+  Dense x = dense16_of(X, "X"), c = dense16_of(C, "C");
   TORCH_CHECK(x.F == 128 && c.F == 128, "X and C must have 128 columns (the decoder's lin1 width), got ", x.F, " and ", c.F);
   check(W2, at::kFloat, 2, "W2", X);
   TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
@@ -514,9 +534,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_row_topk(const Tensor& X, co
   Tensor out_count = at::empty({x.rows}, opts.dtype(at::kInt));
   Tensor info = at::zeros({2}, opts.dtype(at::kInt));
   if (x.rows == 0) return {out_cand, out_logit, out_count, info};
-  Tensor W2c = W2.contiguous(), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.t.data_ptr()) & 15) == 0 && (reinterpret_cast<uintptr_t>(c.t.data_ptr()) & 15) == 0 &&
-                  x.ld % 4 == 0 && c.ld % 4 == 0, "X and C rows must be 16-B aligned");
+  Tensor W2c = contiguous16(W2), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK(rows_16b_aligned(x.t, x.ld) && rows_16b_aligned(c.t, c.ld), "X and C rows must be 16-B aligned");
   // per call, from the caching allocator, as pair_mlp_topk
   const size_t wbytes = dgmi_row_topk_workspace_bytes(x.rows, c.rows, (int32_t)k);
   Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
