@@ -16,7 +16,9 @@ The package holds only what the path needs:
 * ``synth``    — device-side generators for the synthetic configs;
 * ``shard``    — nnz-balanced edge partition + RCCL exchange for the multi-GPU configs;
 * ``predict``  — ``top_novel_pairs``: the k best novel drug-disease pairs of a trained ``Net`` (train.py:26-151);
-  ``top_novel_per_disease`` / ``top_novel_per_drug``: the k best novel candidates of every disease / drug.
+  ``top_novel_per_disease`` / ``top_novel_per_drug``: the k best novel candidates of every disease / drug;
+  ``novel_pairs_above`` / ``count_novel_pairs_above`` / ``top_novel_pairs_deep``: every novel pair at or above a score
+  cut, their exact number, and the k best for k beyond the on-chip limit.
 
 There is no CPU fallback: every op raises if ``libdgmi.so`` is missing or a tensor is
 not on a HIP device.
@@ -24,8 +26,9 @@ not on a HIP device.
 from . import _lib  # noqa: F401  (fails loudly if the extension is not built)
 from .ops import (CSRGraph, EdgePairs, SlicedCSR, SpmmPlan, csr_from_coo, gather_add, gather_concat,  # noqa: F401
                   random_subset_mask, spmm_csr)
-from .predict import NovelLists, NovelPairs, top_novel_pairs, top_novel_per_disease, top_novel_per_drug  # noqa: F401
+from .predict import (NovelLists, NovelPairs, count_novel_pairs_above, novel_pairs_above, top_novel_pairs,  # noqa: F401
+                      top_novel_pairs_deep, top_novel_per_disease, top_novel_per_drug)
 
 __all__ = ["CSRGraph", "EdgePairs", "SlicedCSR", "SpmmPlan", "csr_from_coo", "gather_add", "gather_concat",
            "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs", "NovelLists", "top_novel_per_disease",
-           "top_novel_per_drug"]
+           "top_novel_per_drug", "novel_pairs_above", "count_novel_pairs_above", "top_novel_pairs_deep"]

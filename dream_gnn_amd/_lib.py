@@ -90,6 +90,17 @@ RANK_SIGNATURES = {
 }
 ROW_TOPK_MAX_K = 128  # DGMI_ROW_TOPK_MAX_K
 
+# name -> (restype, argtypes); mirrors include/dgmi_above.h (a fourth table, for the same reason).
+ABOVE_SIGNATURES = {
+    "dgmi_pair_emit_workspace_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "dgmi_pair_mlp_emit_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _i64, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              ctypes.c_size_t, _vp]),
+    "dgmi_pair_records_sort_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "dgmi_pair_records_sort_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_size_t, _vp]),
+}
+PAIR_EMIT_MAX_RECORDS = 1 << 24  # DGMI_PAIR_EMIT_MAX_RECORDS
+
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
 
@@ -100,8 +111,9 @@ def _load() -> ctypes.CDLL:
             "dream_gnn_amd: %s is missing. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C dream_gnn_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what dgmi.h / dgmi_pairs.h / dgmi_rank.h declare
+    for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
+                              + list(ABOVE_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the four headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

@@ -25,6 +25,7 @@
 #include <unordered_map>
 
 #include "dgmi.h"
+#include "dgmi_above.h"
 #include "dgmi_pairs.h"
 #include "dgmi_rank.h"
 
@@ -78,7 +79,7 @@ Tensor scratch(const Tensor& like, size_t nbytes, int kind) {
   }
   return it->second;
 }
-enum { kPartials = 0, kPlanes = 1, kBuilder = 2 };
+enum { kPartials = 0, kPlanes = 1, kBuilder = 2, kPairs = 3 };
 
 struct Keep {
   const int32_t* eid = nullptr;
@@ -549,6 +550,80 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_row_topk(const Tensor& X, co
   return {out_cand, out_logit, out_count, info};
 }
 
+// every novel pair whose decoder logit reaches `min_logit` (dgmi_pairs_above.hip), appended in scheduling order to the
+// caller's record tensors (capacity = their length; 0 = count only): returns count = [the exact int64 number of
+// qualifying pairs, which may exceed the capacity] and info = [0, out-of-range flag].  Nothing is written past the
+// capacity.  Known ids as in pair_mlp_topk; the bitmap lives in the per-(device, stream) scratch; nothing synchronises.
+std::tuple<Tensor, Tensor> pair_mlp_emit(const Tensor& P, const Tensor& Q, const Tensor& W2, const Tensor& b2, const Tensor& w3,
+                                         const Tensor& b3, const OptTensor& known_drug, const OptTensor& known_dis,
+                                         double min_logit, Tensor out_drug, Tensor out_dis, Tensor out_logit) {
+  Dense p = dense16_of(P, "P"), q = dense16_of(Q, "Q");
+  TORCH_CHECK(p.F == 128 && q.F == 128, "P and Q must have 128 columns (the decoder's lin1 width), got ", p.F, " and ", q.F);
+  check(W2, at::kFloat, 2, "W2", P);
+  TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
+  check(b2, at::kFloat, 1, "b2", P);
+  check(w3, at::kFloat, 1, "w3", P);
+  check(b3, at::kFloat, 1, "b3", P);
+  TORCH_CHECK(b2.numel() == 64 && w3.numel() == 64 && b3.numel() == 1, "b2 / w3 / b3 must have 64 / 64 / 1 entries");
+  check(out_drug, at::kInt, 1, "out_drug", P);
+  check(out_dis, at::kInt, 1, "out_dis", P);
+  check(out_logit, at::kFloat, 1, "out_logit", P);
+  const int64_t capacity = out_drug.numel();
+  TORCH_CHECK(out_dis.numel() == capacity && out_logit.numel() == capacity, "out_drug / out_dis / out_logit length mismatch");
+  TORCH_CHECK(capacity <= DGMI_PAIR_EMIT_MAX_RECORDS, "at most ", DGMI_PAIR_EMIT_MAX_RECORDS, " records per pass, got ", capacity);
+  const bool has_known = known_drug.has_value() && known_drug->defined();
+  TORCH_CHECK(has_known == (known_dis.has_value() && known_dis->defined()), "known_drug and known_dis go together");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(p.t.device());
+  Tensor kd, ks;
+  if (has_known) {
+    for (const Tensor* t : {&*known_drug, &*known_dis}) {
+      check_dev(*t, "known ids");
+      TORCH_CHECK(t->dim() == 1 && (t->scalar_type() == at::kInt || t->scalar_type() == at::kLong) && t->device() == P.device(),
+                  "known ids must be 1-D int32 / int64 tensors on ", P.device().str());
+    }
+    TORCH_CHECK(known_drug->numel() == known_dis->numel(), "known_drug / known_dis length mismatch");
+    auto i32 = [](const Tensor& t) {
+      return t.scalar_type() == at::kInt ? t.contiguous() : t.clamp(-1, (int64_t)INT32_MAX).to(at::kInt).contiguous();
+    };
+    kd = i32(*known_drug);
+    ks = i32(*known_dis);
+  }
+  const int64_t n_known = has_known ? kd.numel() : 0;
+  auto opts = p.t.options();
+  Tensor count = at::zeros({1}, opts.dtype(at::kLong)), info = at::zeros({2}, opts.dtype(at::kInt));
+  if (p.rows == 0 || q.rows == 0) return {count, info};
+  Tensor W2c = contiguous16(W2), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK(rows_16b_aligned(p.t, p.ld) && rows_16b_aligned(q.t, q.ld), "P and Q rows must be 16-B aligned");
+  const size_t wbytes = dgmi_pair_emit_workspace_bytes(p.rows, q.rows);
+  Tensor ws = scratch(p.t, wbytes < 256 ? 256 : wbytes, kPairs);
+  check_status(dgmi_pair_mlp_emit_f32(p.t.data_ptr<float>(), p.ld, p.rows, q.t.data_ptr<float>(), q.ld, q.rows, 128, 64,
+                                      W2c.data_ptr<float>(), b2c.data_ptr<float>(), w3c.data_ptr<float>(), b3c.data_ptr<float>(),
+                                      has_known ? kd.data_ptr<int32_t>() : nullptr, has_known ? ks.data_ptr<int32_t>() : nullptr,
+                                      n_known, (float)min_logit, capacity, capacity ? out_drug.data_ptr<int32_t>() : nullptr,
+                                      capacity ? out_dis.data_ptr<int32_t>() : nullptr,
+                                      capacity ? out_logit.data_ptr<float>() : nullptr, count.data_ptr<int64_t>(),
+                                      info.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(p.t)),
+               "dgmi_pair_mlp_emit_f32");
+  return {count, info};
+}
+
+// the first n records of (drug, dis, logit) into the ranking order, in place (dgmi_pair_records_sort_f32): logit
+// descending, ties by (drug, dis) ascending, NaN last
+void pair_records_sort(Tensor drug, Tensor dis, Tensor logit, int64_t n) {
+  check(drug, at::kInt, 1, "drug", drug);
+  check(dis, at::kInt, 1, "dis", drug);
+  check(logit, at::kFloat, 1, "logit", drug);
+  TORCH_CHECK(n >= 0 && n <= drug.numel() && n <= dis.numel() && n <= logit.numel(), "n = ", n, " is outside the record tensors");
+  TORCH_CHECK(n <= DGMI_PAIR_EMIT_MAX_RECORDS, "at most ", DGMI_PAIR_EMIT_MAX_RECORDS, " records per sort, got ", n);
+  if (n == 0) return;
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(drug.device());
+  const size_t wbytes = dgmi_pair_records_sort_workspace_bytes(n);
+  Tensor ws = scratch(drug, wbytes < 256 ? 256 : wbytes, kPairs);
+  check_status(dgmi_pair_records_sort_f32(drug.data_ptr<int32_t>(), dis.data_ptr<int32_t>(), logit.data_ptr<float>(), n,
+                                          ws.data_ptr(), (size_t)ws.numel(), stream_of(drug)),
+               "dgmi_pair_records_sort_f32");
+}
+
 // `like`: any tensor on the target device (the op needs a device to allocate on)
 Tensor random_subset_select(const Tensor& like, int64_t E, int64_t keep, int64_t seed, int64_t e_offset) {
   check_dev(like, "like");
@@ -753,6 +828,9 @@ TORCH_LIBRARY(dreamgnn_mi, m) {
         "int k) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("pair_mlp_row_topk(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_query, "
         "Tensor? known_cand, int k) -> (Tensor cand, Tensor logit, Tensor count, Tensor info)");
+  m.def("pair_mlp_emit(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_drug, Tensor? known_dis, "
+        "float min_logit, Tensor(a!) out_drug, Tensor(b!) out_dis, Tensor(c!) out_logit) -> (Tensor count, Tensor info)");
+  m.def("pair_records_sort(Tensor(a!) drug, Tensor(b!) dis, Tensor(c!) logit, int n) -> ()");
   m.def("scale_rows(Tensor X, Tensor scale) -> Tensor");
   m.def("colsum_rows_(Tensor(a!) feat_ext, Tensor coef, int n, int R, int i0) -> ()");
   m.def("colsum_rows_backward_(Tensor(a!) gf, Tensor coef, Tensor gs, int n, int R, int i0) -> ()");
@@ -782,6 +860,8 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
   m.impl("knn_cosine_topk", knn_cosine_topk);
   m.impl("pair_mlp_topk", pair_mlp_topk);
   m.impl("pair_mlp_row_topk", pair_mlp_row_topk);
+  m.impl("pair_mlp_emit", pair_mlp_emit);
+  m.impl("pair_records_sort", pair_records_sort);
   m.impl("scale_rows", scale_rows);
   m.impl("colsum_rows_", colsum_rows_);
   m.impl("colsum_rows_backward_", colsum_rows_backward_);

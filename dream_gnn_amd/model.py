@@ -242,6 +242,66 @@ class MLPDecoder(nn.Module):
                                                    self.lin3.bias, kq, kc, k)
         return query_id, cand, logit, count
 
+    def _split_lin1(self, drug_feat, dis_feat):
+        """``(P, Q)`` with the torch expressions of :meth:`top_pairs`, so that the kernels see the same bits."""
+        Fd = drug_feat.shape[1]
+        w1 = self.lin1.weight
+        return torch.addmm(self.lin1.bias, drug_feat, w1[:, :Fd].t()), dis_feat @ w1[:, Fd:].t()
+
+    def _tail(self):
+        return self.lin2.weight, self.lin2.bias, self.lin3.weight, self.lin3.bias
+
+    def pairs_above(self, drug_feat, dis_feat, min_logit, known=None, max_pairs=1 << 20):
+        """EVERY (drug, disease) pair not in ``known = (drug_ids, disease_ids)`` whose eval-mode logit is at or above
+        ``min_logit`` (``ops.pair_mlp_above``): ``(drug_id, disease_id, logit)`` device tensors in the order of
+        :meth:`top_pairs`, every logit bit-identical to the one :meth:`top_pairs` computes for the pair.  The cut is
+        inclusive; ``min_logit = NaN`` lists every novel pair.  Raises ``ops.TooManyPairs`` (with the exact count) when
+        more than ``max_pairs`` (1..2**24) pairs qualify."""
+        max_pairs = ops._check_max_pairs(max_pairs)
+        P, Q = self._split_lin1(drug_feat, dis_feat)
+        kd, ks = (None, None) if known is None else known
+        return ops.pair_mlp_above(P, Q, *self._tail(), kd, ks, float(min_logit), max_pairs)[:3]
+
+    def count_pairs_above(self, drug_feat, dis_feat, min_logit, known=None):
+        """How many pairs :meth:`pairs_above` lists at this cut (``ops.pair_mlp_count_above``): exact, nothing stored."""
+        P, Q = self._split_lin1(drug_feat, dis_feat)
+        kd, ks = (None, None) if known is None else known
+        return ops.pair_mlp_count_above(P, Q, *self._tail(), kd, ks, float(min_logit))
+
+    #: the largest ``k`` of :meth:`top_pairs_deep`
+    DEEP_MAX_K = 1 << 20
+
+    def top_pairs_deep(self, drug_feat, dis_feat, k, known=None):
+        """:meth:`top_pairs` for ``1 <= k <= 2**20``: the same tuple, order and logit bits.  Up to 1024 it is
+        :meth:`top_pairs`; beyond, a cut is estimated from every s-th drug row (``s = ceil(k / 512)``, scored by the
+        on-chip top-k without the known list: the sample's entry at rank ``ceil(1.5 k / s) + 32``), one emit pass lists
+        every novel pair at or above it into ``4 k + 65536`` slots, and the sorted list is cut at ``k``.  A pass that
+        returns fewer than ``k`` pairs is repeated with a lower cut (twice the sample rank, then no cut): at most three.
+
+        The estimate only decides how much is emitted: a pass lists EVERY novel pair at or above its cut and counts
+        them exactly, so once the count is at least ``k`` (or there is no cut) and within the buffer, the ``k`` best
+        of all pairs are among the listed ones and the sorted prefix is the exact answer.  A count beyond the buffer
+        raises ``ops.TooManyPairs`` instead of returning a truncated list."""
+        k = int(k)
+        if not 1 <= k <= self.DEEP_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (self.DEEP_MAX_K, k))
+        if k <= ops.PAIR_TOPK_MAX_K:
+            return self.top_pairs(drug_feat, dis_feat, k, known)
+        P, Q = self._split_lin1(drug_feat, dis_feat)
+        tail = self._tail()
+        kd, ks = (None, None) if known is None else known
+        s = -(-k // 512)
+        rank = -(-3 * k // (2 * s)) + 32
+        sample = ops.pair_mlp_topk(P[::s], Q, *tail, None, None, ops.PAIR_TOPK_MAX_K)[2]
+        capacity = 4 * k + 65536
+        nan = float("nan")
+        for r in (rank, 2 * rank, None):
+            everything = r is None or sample.numel() < r
+            cut = nan if everything else float(sample[r - 1])
+            drug, dis, logit, n = ops.pair_mlp_above(P, Q, *tail, kd, ks, cut, capacity)
+            if n >= k or everything or cut != cut:
+                break
+        return drug[:k], dis[:k], logit[:k]
 
 def query_rows(rows, n_query: int):
     """``rows`` as a CPU int64 tensor of unique query ids in ``[0, n_query)``, or None; ``ValueError`` otherwise."""

@@ -1150,6 +1150,71 @@ def pair_mlp_row_topk(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: to
                            % (X.shape[0], C.shape[0]))
     return cand.long(), logit, count
 
+
+# ---------------------------------------------------------------------------------------------
+# every novel pair at or above a cut — the list a top-k cannot give, and the carrier of k > 1024
+# ---------------------------------------------------------------------------------------------
+PAIR_EMIT_MAX_RECORDS = _lib.PAIR_EMIT_MAX_RECORDS
+
+
+class TooManyPairs(RuntimeError):
+    """More pairs reach the cut than the caller allowed: ``count`` (exact) > ``max_pairs``.  Nothing is returned."""
+
+    def __init__(self, count: int, max_pairs: int):
+        super().__init__("%d novel pairs reach the cut, more than max_pairs = %d: raise the cut or max_pairs"
+                         % (count, max_pairs))
+        self.count = int(count)
+        self.max_pairs = int(max_pairs)
+
+
+def _check_max_pairs(max_pairs) -> int:
+    max_pairs = int(max_pairs)
+    if not 1 <= max_pairs <= PAIR_EMIT_MAX_RECORDS:
+        raise ValueError("max_pairs must be in 1..%d (the record buffer limit), got %d" % (PAIR_EMIT_MAX_RECORDS, max_pairs))
+    return max_pairs
+
+
+def _pair_emit(P, Q, W2, b2, w3, b3, known_drug, known_dis, min_logit, capacity):
+    """One emit pass into fresh record tensors of ``capacity`` slots: ``(drug, dis, logit, count)`` with the exact
+    count as a Python int (the one host sync).  The records are unsorted; ``count`` may exceed ``capacity``."""
+    _require_device(P, Q, W2, b2, w3, b3, known_drug, known_dis)
+    drug = torch.empty(capacity, dtype=torch.int32, device=P.device)
+    dis = torch.empty_like(drug)
+    logit = torch.empty(capacity, dtype=torch.float32, device=P.device)
+    count, info = _T.pair_mlp_emit(P, Q, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), known_drug, known_dis,
+                                   float(min_logit), drug, dis, logit)
+    n, _, bad = (int(v) for v in torch.cat([count, info.long()]).tolist())  # one read for both
+    if bad:
+        raise RuntimeError("pair_mlp_emit: a known (drug, disease) id is outside [0, %d) x [0, %d)"
+                           % (P.shape[0], Q.shape[0]))
+    return drug, dis, logit, n
+
+
+def pair_mlp_above(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                   b3: torch.Tensor, known_drug: Optional[torch.Tensor], known_dis: Optional[torch.Tensor],
+                   min_logit: float, max_pairs: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, int]:
+    """EVERY pair ``(i, j)`` not in ``(known_drug, known_dis)`` whose logit (that of :func:`pair_mlp_topk`, the same
+    bits) is at or above ``min_logit`` (``dgmi_pair_mlp_emit_f32`` then ``dgmi_pair_records_sort_f32``), ordered by
+    logit descending, ties by ``(i, j)`` ascending, NaN last.  The cut is inclusive in fp32, -0 and +0 are one value, a
+    NaN logit reaches no numeric cut (-inf included); ``min_logit = NaN`` selects every novel pair, NaN logits included.
+    Returns int64 drug ids, int64 disease ids, fp32 logits on the device and the exact count (their length); the only
+    host sync is reading the count and the flag.  Raises :class:`TooManyPairs` (with the exact ``count``) when more
+    than ``max_pairs`` pairs qualify, ``ValueError`` for ``max_pairs`` outside 1..2**24 and ``RuntimeError`` when a
+    known id is out of range."""
+    max_pairs = _check_max_pairs(max_pairs)
+    drug, dis, logit, n = _pair_emit(P, Q, W2, b2, w3, b3, known_drug, known_dis, min_logit, max_pairs)
+    if n > max_pairs:
+        raise TooManyPairs(n, max_pairs)
+    _T.pair_records_sort(drug, dis, logit, n)
+    return drug[:n].long(), dis[:n].long(), logit[:n], n
+
+
+def pair_mlp_count_above(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                         b3: torch.Tensor, known_drug: Optional[torch.Tensor], known_dis: Optional[torch.Tensor],
+                         min_logit: float) -> int:
+    """How many pairs :func:`pair_mlp_above` would list at this cut, without storing any (capacity 0): exact, no limit."""
+    return _pair_emit(P, Q, W2, b2, w3, b3, known_drug, known_dis, min_logit, 0)[3]
+
 # ---------------------------------------------------------------------------------------------
 # (D3) edge-dropout selection — augmentation.py:48-52, 114-118
 # ---------------------------------------------------------------------------------------------

@@ -16,6 +16,11 @@ logits last.  Wherever the reference's own scores are distinct, the two orders a
 new indications fit drug Y): the k best novel candidates of every query row, from one HIP kernel over the same scorer
 (``MLPDecoder.top_pairs_per_row``, ``csrc/dgmi_pairs_rows.hip``).  Within a row the order is the global one restricted
 to that row: logit descending, ties by candidate id ascending, NaN last.
+
+``novel_pairs_above`` / ``count_novel_pairs_above`` ask by score instead of by count (every novel pair the model puts at
+or above a cut, and how many there are), and ``top_novel_pairs_deep`` ranks beyond the on-chip limit (``k`` up to 2**20):
+one streaming HIP kernel over the same scorer emits the qualifying pairs with an exact count, a device sort orders them
+(``MLPDecoder.pairs_above`` / ``top_pairs_deep``, ``csrc/dgmi_pairs_above.hip``).  Same order, same logit bits.
 """
 from __future__ import annotations
 
@@ -27,8 +32,13 @@ import torch
 from . import ops
 from .model import query_rows
 
-#: the largest ``k`` the on-chip top-k takes; there is no other path
+#: the largest ``k`` the on-chip top-k takes; there is no other path inside :func:`top_novel_pairs` (for a deeper
+#: list see :func:`top_novel_pairs_deep`, for a list by score :func:`novel_pairs_above`)
 MAX_K = ops.PAIR_TOPK_MAX_K
+#: the largest ``k`` of :func:`top_novel_pairs_deep`
+DEEP_MAX_K = 1 << 20
+#: the largest ``max_pairs`` of :func:`novel_pairs_above`
+MAX_PAIRS = ops.PAIR_EMIT_MAX_RECORDS
 #: the largest ``k`` per row of the per-disease / per-drug lists
 ROW_MAX_K = ops.ROW_TOPK_MAX_K
 
@@ -193,3 +203,79 @@ def top_novel_per_drug(net, batch, known, k: int = 10, drugs=None) -> NovelLists
     ``net`` scores highest: its best new indications.  Otherwise as :func:`top_novel_per_disease`; ties by disease id
     ascending."""
     return _top_novel_lists(net, batch, known, k, "drug", drugs)
+
+
+def _cut_logit(min_score, min_logit) -> float:
+    """The one cut, as an fp32 logit: ``min_logit`` itself, or ``log(p / (1 - p))`` of ``min_score = p`` computed in
+    float64 and rounded once to float32."""
+    if (min_score is None) == (min_logit is None):
+        raise ValueError("give exactly one of min_score and min_logit")
+    if min_logit is not None:
+        return float(np.float32(min_logit))
+    p = float(min_score)
+    if not 0.0 < p < 1.0:
+        raise ValueError("min_score must lie in (0, 1), got %r (use min_logit for a cut on the logit)" % (min_score,))
+    return float(np.float32(np.log(np.float64(p) / (np.float64(1.0) - np.float64(p)))))
+
+
+def _with_embedding(net, batch, fn):
+    """``fn(hd, hs)`` on the eval-mode embeddings, under ``no_grad``; the net's training flag is restored."""
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            hd, hs = net.embed(batch["enc_graph"], batch["drug_graph"], batch["drug_sim_feat"], batch["drug_feat"],
+                               batch["disease_graph"], batch["disease_sim_feat"], batch["disease_feat"],
+                               batch.get("drug_feature_graph"), batch.get("disease_feature_graph"))
+            return fn(hd, hs)
+    finally:
+        net.train(was_training)
+
+
+def _known_of(batch, known):
+    n_drug, n_dis = int(batch["drug_feat"].shape[0]), int(batch["disease_feat"].shape[0])
+    kd, ks = _known_ids(known, n_drug, n_dis, batch["drug_feat"].device)
+    return None if kd is None else (kd, ks)
+
+
+def _novel_pairs(drug, dis, logit) -> NovelPairs:
+    logit = logit.cpu()
+    return NovelPairs(drug.cpu(), dis.cpu(), logit, torch.sigmoid(logit))
+
+
+def novel_pairs_above(net, batch, known, min_score=None, min_logit=None, max_pairs: int = 1 << 20) -> NovelPairs:
+    """EVERY pair not in ``known`` that ``net`` puts at or above a cut, eval mode, in the order of
+    :func:`top_novel_pairs`.  ``batch`` and ``known`` as there.  Exactly one of ``min_score`` (a probability in (0, 1))
+    and ``min_logit`` is given; ``min_logit = NaN`` lists every novel pair.
+
+    The cut is applied to the LOGIT: ``min_score = p`` is translated once to ``float32(log(p / (1 - p)))`` (computed in
+    float64) and a pair qualifies iff its fp32 logit is >= that value, inclusive.  The fp32 sigmoid is not compared, for
+    the reason the module docstring gives: it saturates to exactly 1.0 and is not one-to-one, so a cut on it would not
+    name a set.  A returned ``score`` can therefore differ from ``min_score`` by an ulp on either side.
+
+    Raises ``ops.TooManyPairs`` (``.count`` exact, ``.max_pairs``) when more than ``max_pairs`` (1..2**24) pairs
+    qualify: the list is never truncated silently.  Validates ``known``, the cut and ``max_pairs`` before the model
+    runs; the encoder runs once under ``no_grad`` and the training flag is restored."""
+    cut = _cut_logit(min_score, min_logit)
+    max_pairs = ops._check_max_pairs(max_pairs)
+    kn = _known_of(batch, known)
+    return _novel_pairs(*_with_embedding(net, batch, lambda hd, hs: net.decoder.pairs_above(hd, hs, cut, kn, max_pairs)))
+
+
+def count_novel_pairs_above(net, batch, known, min_score=None, min_logit=None) -> int:
+    """How many pairs :func:`novel_pairs_above` lists at this cut: exact, without a limit, nothing stored."""
+    cut = _cut_logit(min_score, min_logit)
+    kn = _known_of(batch, known)
+    return int(_with_embedding(net, batch, lambda hd, hs: net.decoder.count_pairs_above(hd, hs, cut, kn)))
+
+
+def top_novel_pairs_deep(net, batch, known, k: int) -> NovelPairs:
+    """:func:`top_novel_pairs` for ``1 <= k <= 2**20``: the ``min(k, #novel)`` best novel pairs in the same order, exact
+    (``MLPDecoder.top_pairs_deep``: a sampled cut, one emit pass with an exact count, a device sort).  Raises
+    ``ops.TooManyPairs`` if a pass finds more pairs than its ``4 k + 65536`` slots hold.  Validates ``k`` and ``known``
+    before the model runs; the encoder runs once under ``no_grad`` and the training flag is restored."""
+    k = int(k)
+    if not 1 <= k <= DEEP_MAX_K:
+        raise ValueError("k must be in 1..%d, got %d" % (DEEP_MAX_K, k))
+    kn = _known_of(batch, known)
+    return _novel_pairs(*_with_embedding(net, batch, lambda hd, hs: net.decoder.top_pairs_deep(hd, hs, k, kn)))
