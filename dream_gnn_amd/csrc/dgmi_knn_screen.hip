@@ -4,11 +4,13 @@
 // scale (reference data_loader.py:312-344 on N >> 10^4 rows) the neighbour SEARCH is done on the bf16
 // matrix cores, and the answer is still the fp32 one — by a bound, not by hope:
 //
-//   rows are L2-normalised, bf16 rounding is |d| <= 2^-9 per element, bf16 x bf16 products are exact in
-//   the fp32 accumulator, so  |approx(q, c) - <q, c>| <= (2^-8 + 2^-18) |q| |c| + fp32 summation error
-//   <= kScreenEps.  Let tau = the k-th largest approx score of query q.  k candidates have an exact
-//   score >= tau - eps, so every member of the exact top-k has exact >= tau - eps, hence
-//   approx >= tau - 2 eps.  Any lower bound tau' <= tau only enlarges that set.
+//   rows are L2-normalised, bf16 (8 significant bits, round to nearest even) moves an element by at most
+//   u = 2^-8 of its size, |x~ - x| <= u |x|, bf16 x bf16 products are exact in the fp32 accumulator, so
+//   |approx(q, c) - <q, c>| <= ((1 + u)^2 - 1) sum |q_i| |c_i| <= (2^-7 + 2^-16) |q| |c| + fp32 summation error
+//   <= kScreenEps (derived at its definition; the bound is attained to 60 %: tests/_knn_cases.py).  Let tau = the
+//   k-th largest approx score of query q.  k candidates have an exact score >= tau - eps, so every member of the
+//   exact top-k has exact >= tau - eps, hence approx >= tau - 2 eps.  Any lower bound tau' <= tau only enlarges
+//   that set.
 //
 // Pipeline (all on one stream, no host round trip):
 //   1. knn_to_bf16_kernel        Xn -> bf16 copy, rows / columns zero-padded to 128 / 64
@@ -62,7 +64,16 @@ constexpr int kSK = 64;   // bf16 per K chunk (128 B per row)
 constexpr int kSplits = 8;
 constexpr int kScreenBigMinRows = 49152;  // 256 x 256 tiles: slower at 20 000 rows (1.34 vs 1.17 ms), 10 % faster at 100 000
 constexpr int kScreenMinRows = 1536;  // measured crossover against the fp32 kernel (tools/knn_crossover.py)
-constexpr float kScreenEps = 0.0042f;                // 2^-8 + 2^-18 + slack for fp32 accumulation / norms
+// eps of the header: a bound of |approx - exact| for EVERY pair of rows, whichever kernel and direction computed approx.
+//   bf16 rounding     (1 + 2^-8)^2 - 1 = 2^-7 + 2^-16                                     = 0.0078278  (x |q| |c|)
+//   fp32 accumulation the MFMA adds Dp <= 1024 exact products in an order of its own; each add is off by at most
+//                     2^-23 of the partial sum (one ulp: covers an accumulator that truncates), the partial sums
+//                     are <= sum |q~_i| |c~_i| <= (1 + 2^-8)^2: 1024 x 2^-23 x 1.0079                = 0.0001231
+//   norms             callers normalise in fp32: |x| = 1 within 1e-5 at the very worst, so |q| |c| <= 1 + 2.1e-5
+//                     and the first line grows by 0.0078278 x 2.1e-5                                  = 0.0000002
+// Sum 0.0079511; 0.008 leaves 4.9e-5.  (0.0042, the first value, took the per-element rounding for 2^-9: designed rows
+// reach |approx - exact| = 0.0047, and a true neighbour 0.0091 below the decoys' approx score was never rescored.)
+constexpr float kScreenEps = 0.008f;
 constexpr float kUnset = -2.0f;                      // below every cosine; list filler
 constexpr float kMasked = -4.0f;                     // score given to padding candidates
 
@@ -1038,7 +1049,7 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     return;
   }
   if (lane == 0) flags[q] = 0;
-  const float tau = kJ >= 32 ? wave_kth_largest_bisect<kJ>(work, k) : wave_kth_largest<kJ>(work, k, lane);
+  const float tau = kJ >= 64 ? wave_kth_largest_bisect<kJ>(work, k) : wave_kth_largest<kJ>(work, k, lane);
   const float keep_from = tau - 2.f * kScreenEps;
 
   // the query row, 16 B per lane per 256 columns
@@ -1050,9 +1061,9 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
 
   float best_s = kMasked;  // lane i < k: the i-th best (score desc, id asc)
   int32_t best_id = 0x7fffffff;
-  if constexpr (kJ < 32) {
-    // short buffers (k <= 8): few registers, many waves per SIMD — they hide the latency of one entry after the other
-    // (batched like the long ones this pass went 0.56 -> 0.90 ms at N = 100 000, k = 4)
+  if constexpr (kJ < 64) {
+    // short buffers (k <= 8; k <= 16 on the full rectangle): few registers, many waves per SIMD — they hide the latency of one
+    // entry after the other (batched like the long ones this pass went 0.56 -> 0.90 ms at N = 100 000, k = 4)
 #pragma unroll
     for (int i = 0; i < kJ; ++i) {
       uint64_t todo = __ballot(e_s[i] >= keep_from);
@@ -1178,8 +1189,13 @@ ScreenLayout screen_layout(int64_t N, int64_t D, int k) {
   const int tile = L.big ? Shape<true>::kTile : Shape<false>::kTile;
   L.Np = (int)((N + tile - 1) / tile * tile);
   L.Dp = (int)((D + kSK - 1) / kSK * kSK);
-  L.cap_r = k <= 8 ? 64 : (k <= 16 ? 128 : 256);  // slots per (query, candidate split) region
   L.sym = screen_sym(N, k);
+  // slots per (query, candidate split) region.  Sized on random unit rows at D = 768 for the 2 eps = 0.016 margin (which keeps
+  // twice the pairs 2 x 0.0042 kept): the fullest region of any query at N = 100 000 held 72 / 151 / 183 entries at k = 4 / 16 /
+  // 64 (triangular sweep), and on the full rectangle, where the row regions take both directions, 256 no longer held k = 64 at
+  // N = 20 000.  A region that overflows is not an error but sends its query's tile to the exact take-over: 8 such queries
+  // of 100 000 took the k = 4 search from 12 to 35 ms.
+  L.cap_r = k <= 8 ? 128 : (k <= 16 || L.sym ? 256 : 512);
   L.cap_c = L.sym ? kSplits * L.cap_r : 0;  // slots of the column-direction region (triangular sweep only)
   size_t at = 0;
   L.xb = at, at += align256((size_t)L.Np * L.Dp * 2);
@@ -1189,10 +1205,12 @@ ScreenLayout screen_layout(int64_t N, int64_t D, int k) {
   L.cnt = at, at += align256((size_t)N * (kSplits + 1) * 4);
   L.buf = at, at += align256((size_t)N * (kSplits * L.cap_r + L.cap_c) * 8);
   L.flags = at, at += align256((size_t)N * 4);
-  // the phase-interleaved 256 x 256 kernel keeps ~ 18 k pairs per query (tau' comes from an eighth of the candidates, the
-  // 2 eps margin); the half of them that its triangular sweep offers to the queries of OTHER tiles goes through the pool:
-  // room for 16 k + 48 per query, in chunks (each wave of each workgroup holds one partly filled chunk: the 2048)
-  const size_t want_chunks = ((size_t)N * (16 * k + 48) + kChunk - 1) / kChunk + 2048;
+  // the phase-interleaved 256 x 256 kernel keeps 150 / 510 / 940 pairs per query at k = 4 / 16 / 64 (N = 100 000, D = 768: tau'
+  // comes from an eighth of the candidates, the 2 eps margin); the half of them that its triangular sweep offers to the
+  // queries of OTHER tiles goes through the pool, in chunks that are handed out whole (10.7 M slots for 7.3 M records at
+  // k = 4): room for 20 k + 112 per query, 1.5 x what those runs drew (each wave of each workgroup holds one partly filled
+  // chunk: the 2048)
+  const size_t want_chunks = ((size_t)N * (20 * k + 112) + kChunk - 1) / kChunk + 2048;
   L.pool_chunks = L.big ? (int)(want_chunks < ((size_t)1 << 30) ? want_chunks : ((size_t)1 << 30)) : 0;
   if (L.pool_chunks != 0 && tuning().knn_pool_chunks > 0) L.pool_chunks = (int)tuning().knn_pool_chunks;  // (test: a pool that runs out)
   L.pool = at, at += align256((size_t)L.pool_chunks * kChunk * 16);
@@ -1289,7 +1307,6 @@ hipError_t knn_cosine_topk_screened(const float* Xn, int64_t ld, int64_t N, int6
 #define DGMI_RESCORE(J) \
   hipLaunchKernelGGL(knn_rescore_kernel<J>, rgrid, dim3(256), 0, s, Xn, ld, (int)N, (int)D, k, L.cap_r, L.cap_c, cnt, buf, nbr, flags)
   switch ((kSplits * L.cap_r + L.cap_c) / 64) {  // buffer slots per lane
-    case 8: DGMI_RESCORE(8); break;
     case 16: DGMI_RESCORE(16); break;
     case 32: DGMI_RESCORE(32); break;
     default: DGMI_RESCORE(64); break;

@@ -3,6 +3,8 @@
 Tolerances (north_star): CSR indexing bit-exact; fp32 embeddings within 1e-5 relative
 (see _check_close for what "relative" is measured against).
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -775,9 +777,11 @@ def test_fused_knn_kernel_finds_the_k_most_similar_rows(dev, N, D, k):
 
 
 def test_screened_knn_recomputes_overflowing_rows_exactly(dev):
-    """(f4) the bf16 screen keeps at most 64 candidates per (query, candidate split); a cluster of 400
+    """(f4) the bf16 screen keeps at most 128 candidates per (query, candidate split) (256 / 512 at k > 8); a cluster of 400
     near-identical rows puts far more than that within the 2-eps margin of the k-th best, so those queries
-    are flagged and their tiles recomputed by the fp32 kernel — the answer is still the exact top-k."""
+    are flagged and their tiles recomputed by the fp32 kernel — the answer is still the exact top-k.
+    The cluster at the end is 2 600 rows: more than the 1 024 / 2 048 slots of the column region (k = 4 / 12), which
+    takes what the triangular sweep offers a query from the tiles before its own."""
     from dream_gnn_amd import ops
 
     # full rectangle / triangular sweep (both directions overflow) / k > 16: the exact-row take-over kernel
@@ -789,7 +793,7 @@ def test_screened_knn_recomputes_overflowing_rows_exactly(dev):
         X[3000:3400] = X[3000] + 1e-3 * torch.randn(400, D, generator=gen)
         if k > 16:  # enough near-duplicates to overflow the wider regions too
             X[1000:2600] = X[1000] + 1e-3 * torch.randn(1600, D, generator=gen)
-        X[N - 700:N - 100] = X[N - 1] + 1e-3 * torch.randn(600, D, generator=gen)
+        X[N - 2700:N - 100] = X[N - 1] + 1e-3 * torch.randn(2600, D, generator=gen)
         xn = (X / X.norm(dim=1, keepdim=True)).to(dev)
         nbr = ops.knn_cosine_topk(xn, k).long()
         worst = 0.0
@@ -801,6 +805,75 @@ def test_screened_knn_recomputes_overflowing_rows_exactly(dev):
             del sim
         assert worst <= 2e-6
         assert all(len(set(r.tolist())) == k for r in nbr[2990:3410].cpu())
+
+
+@functools.lru_cache(maxsize=None)
+def _randn_unit_rows(N, D):
+    """Seeded unit rows on the host, made once per shape and shared by the cases below (which copy them)."""
+    X = torch.randn(N, D, generator=torch.Generator().manual_seed(1000 * D + N % 1000))
+    return X / X.norm(dim=1, keepdim=True)
+
+
+# (path, N, D, k, row of q, row of A); the k decoys are rows 0 .. k - 1: tile 0, which the sample pass always takes, so
+# tau'(q) >= the k-th decoy's approximate score whatever else is sampled.  q and A sit in no 32-row tile that holds a decoy.
+_WORST_CASE_KNN = [
+    # 128 x 128 tiles, full rectangle of tile pairs; k = 40: the widest regions and the bisection for tau
+    ("rect", 2048, 256, 2, 5 * 128 + 17, 11 * 128 + 70),
+    ("rect", 2048, 768, 4, 5 * 128 + 17, 11 * 128 + 70),
+    ("rect-k40", 2048, 256, 40, 5 * 128 + 17, 11 * 128 + 70),
+    # 128 x 128 tiles, triangular sweep (from 24 576 rows at k <= 8; 193 tiles): id(q) < id(A) offers A
+    # to q through q's row regions, id(q) > id(A) through the column region
+    ("tri-row", 24576 + 128, 256, 2, 50 * 128 + 17, 150 * 128 + 70),
+    ("tri-col", 24576 + 128, 256, 2, 150 * 128 + 70, 50 * 128 + 17),
+    # 256 x 256 tiles, LDS-DMA kernel (knn_screen8_kernel: from 49 152 rows, 2+ K chunks), triangular: own-query appends through
+    # the LDS counters, the other direction through the record pool; and the pair inside one diagonal tile
+    ("dma-row", 49152, 256, 2, 40 * 256 + 17, 150 * 256 + 70),
+    ("dma-col", 49152, 256, 2, 150 * 256 + 70, 40 * 256 + 17),
+    ("dma-diag", 49152, 256, 2, 40 * 256 + 17, 40 * 256 + 200),
+    ("dma-row", 49152, 256, 12, 40 * 256 + 17, 150 * 256 + 70),
+    ("dma-col", 49152, 256, 12, 150 * 256 + 70, 40 * 256 + 17),
+    ("dma-diag", 49152, 256, 12, 40 * 256 + 17, 40 * 256 + 200),
+    # 256 x 256 tiles, register-staged kernel (one K chunk): the D = 64 design (h = 30, 2 low decoy elements)
+    ("big-1chunk-row", 49152, 64, 2, 40 * 256 + 17, 150 * 256 + 70),
+    ("big-1chunk-col", 49152, 64, 2, 150 * 256 + 70, 40 * 256 + 17),
+]
+
+
+@pytest.mark.parametrize("path,N,D,k,q_at,a_at", _WORST_CASE_KNN, ids=["%s-%d-%d-%d" % c[:4] for c in _WORST_CASE_KNN])
+def test_screened_knn_keeps_the_true_neighbour_at_worst_case_bf16_rounding(dev, path, N, D, k, q_at, a_at):
+    """(f4) The screen's margin at the rounding it is a bound FOR (tests/_knn_cases.py; the host proof is
+    tests/test_knn_cases_host.py): q's true nearest neighbour A has a bf16 score ~0.0047 too small, k decoys ~0.0047 too
+    large, so A lies 0.0091 below the decoys that set q's threshold while its exact similarity is 2.3e-4 (D = 64) or
+    3.0e-4 above theirs.  A margin of 2 x 0.0042 never hands A to the exact rescoring and the search returns a decoy in
+    its place: measured on an MI355X with eps = 0.0042, all 13 cases failed, q's list off by 2.96e-4 (D = 256, 768) /
+    2.35e-4 (D = 64) against the 2e-6 allowed and A missing from it; with eps = 0.008 every difference is <= 7.3e-10.
+    k + 1 near-identical rows (the decoys are 0.997 similar to each other) overflow no region, so no query is flagged and
+    the exact take-over cannot cover for the screen."""
+    import _knn_cases as K
+    from dream_gnn_amd import ops
+
+    d = K.build(D, k)
+    xn = K.embed(_randn_unit_rows(N, D), d, q_at, a_at).to(dev)
+    assert ops.knn_cosine_supported(N, D, k) and N >= 1536
+    nbr = ops.knn_cosine_topk(xn, k).long()
+    assert nbr.shape == (N, k) and int(nbr.min()) >= 0 and int(nbr.max()) < N
+    gen = torch.Generator().manual_seed(N + D + k)
+    rows = torch.cat([torch.tensor([q_at, a_at]), torch.arange(k), torch.randperm(N, generator=gen)[:1000]]).to(dev)
+    sim = xn[rows].double() @ xn.double().t()
+    # the design survives the embedding: q's exact top-k is itself, A and decoys — no random row comes near
+    designed = {q_at, a_at} | set(range(k))
+    assert set(torch.topk(sim[0], k).indices.tolist()) <= designed
+    assert float(sim[0, a_at]) - float(sim[0, :k].max()) >= 5e-5
+    sel = nbr[rows]
+    assert all(len(set(r.tolist())) == k for r in sel)  # distinct
+    got = torch.gather(sim, 1, sel)
+    want = torch.topk(sim, k, dim=1).values
+    worst = (got - want).abs().max(dim=1).values
+    print("%s N=%d D=%d k=%d: worst |got - want| q %.3g, A %.3g, decoys %.3g, random rows %.3g; A in q's list: %s"
+          % (path, N, D, k, float(worst[0]), float(worst[1]), float(worst[2:2 + k].max()), float(worst[2 + k:].max()),
+             a_at in sel[0].tolist()))
+    assert float(worst.max()) <= 2e-6  # same similarity multiset (near-ties may swap ids)
+    assert a_at in sel[0].tolist()
 
 
 def test_adjacency_assembly_without_library_sort_or_atomics_is_bit_identical(dev):

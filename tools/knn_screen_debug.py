@@ -22,8 +22,8 @@ big = N >= 49152
 tile = 256 if big else 128
 Np = (N + tile - 1) // tile * tile
 Dp = (D + 63) // 64 * 64
-cap_r = 64 if k <= 8 else (128 if k <= 16 else 256)
 sym = N >= (24576 if k <= 8 else 40960)
+cap_r = 128 if k <= 8 else (256 if k <= 16 or sym else 512)
 cap_c = 8 * cap_r if sym else 0
 at = 0
 xb = at; at += al(Np * Dp * 2)
@@ -33,7 +33,7 @@ thr = at; at += al(Np * 4)
 cnt = at; at += al(N * 9 * 4)
 buf = at; at += al(N * (8 * cap_r + cap_c) * 8)
 flags = at; at += al(N * 4)
-chunks = (N * (16 * k + 48) + 255) // 256 + 2048 if big else 0
+chunks = (N * (20 * k + 112) + 255) // 256 + 2048 if big else 0
 pool = at; at += al(chunks * 256 * 16)
 ctl = at; at += al((chunks + 1) * 4 if chunks else 0)
 print("layout total", at, "==", need)
