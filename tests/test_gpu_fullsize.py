@@ -220,10 +220,21 @@ def test_addresses_beyond_4_gib(oracle, dev):
     g = ops.CSRGraph(dst, src, n_dst, n_src, vals=vals)
     ref = torch.zeros(n_dst, Fw, device=dev, dtype=torch.float64).index_add_(
         0, dst.long(), X.index_select(0, src.long()).double() * vals.double()[:, None])
+    sl = ops.SlicedCSR(dst, src, n_dst, n_src, vals=vals)
     for y in (ops.spmm_csr_raw(g.indptr, g.indices, g.vals, X),            # a wave per row
               ops.spmm_csr_raw(g.indptr, g.indices, g.vals, X, plan=g.plan),  # planned
-              ops.SlicedCSR(dst, src, n_dst, n_src, vals=vals).spmm(X)):      # XCD-sliced
+              sl.spmm(X)):                                                    # XCD-sliced
         assert float((y.double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
+    # the XCD-sliced kernel's 64-bit row addresses in two more template variants: src_scale in the kernel, dropout on the fly
+    ss = torch.ones(n_src, device=dev)
+    ss[-600_000:] = torch.rand(600_000, generator=gen, device=dev) + 0.5
+    kept = ops.keep_mask(ops.random_subset_select(E, int(E * 0.7), 11, dev), E)
+    for y, w in ((sl.spmm(X, ss), vals * ss[src.long()]),
+                 (sl.spmm(X, keep=ops.random_subset_select(E, int(E * 0.7), 11, dev)), vals * kept)):
+        ref_w = torch.zeros(n_dst, Fw, device=dev, dtype=torch.float64).index_add_(
+            0, dst.long(), X.index_select(0, src.long()).double() * w.double()[:, None])
+        assert float((y.double() - ref_w).abs().max()) <= 1e-5 * float(ref_w.abs().max())
+    del sl, ss, ref_w
     # transpose product writes rows beyond the 4 GiB mark of a 9 M-row output
     W = torch.randn(n_dst, Fw, generator=gen, device=dev)
     dx = g.spmm_t(W)
