@@ -25,10 +25,10 @@ not on a HIP device.
 """
 from . import _lib  # noqa: F401  (fails loudly if the extension is not built)
 from .ops import (CSRGraph, EdgePairs, SlicedCSR, SpmmPlan, csr_from_coo, gather_add, gather_concat,  # noqa: F401
-                  random_subset_mask, spmm_csr)
+                  gather_precision, random_subset_mask, spmm_csr)
 from .predict import (NovelLists, NovelPairs, count_novel_pairs_above, novel_pairs_above, top_novel_pairs,  # noqa: F401
                       top_novel_pairs_deep, top_novel_per_disease, top_novel_per_drug)
 
 __all__ = ["CSRGraph", "EdgePairs", "SlicedCSR", "SpmmPlan", "csr_from_coo", "gather_add", "gather_concat",
-           "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs", "NovelLists", "top_novel_per_disease",
+           "gather_precision", "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs", "NovelLists", "top_novel_per_disease",
            "top_novel_per_drug", "novel_pairs_above", "count_novel_pairs_above", "top_novel_pairs_deep"]

@@ -101,6 +101,14 @@ ABOVE_SIGNATURES = {
 }
 PAIR_EMIT_MAX_RECORDS = 1 << 24  # DGMI_PAIR_EMIT_MAX_RECORDS
 
+# name -> (restype, argtypes); mirrors include/dgmi_bf16.h (a fifth table, for the same reason).
+BF16_SIGNATURES = {
+    "dgmi_rows_to_bf16": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "dgmi_spmm_sliced_bf16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64,
+                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t] + _EPI + [_vp]),
+}
+
+
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
 
@@ -112,8 +120,8 @@ def _load() -> ctypes.CDLL:
             "or `make -C dream_gnn_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
-                              + list(ABOVE_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the four headers declare
+                              + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the five headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

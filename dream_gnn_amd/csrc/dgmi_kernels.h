@@ -161,6 +161,34 @@ hipError_t row_multiplicity_f32(const int32_t* indptr, const float* vals, int64_
                                 int32_t* mult, int32_t* fail, hipStream_t s);
 hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s);
 
+// The same product gathering from a bf16 table (dgmi_sliced_bf16.hip): X holds bf16 bit patterns, ldx in elements
+// (a multiple of 8), F a multiple of 8; no source scale (it belongs to rows_to_bf16).  Planes, dst_scale, Y: fp32.
+struct SlicedBf16Args {
+  const int32_t* segptr;
+  const int32_t* indices;
+  const float* vals;       // nullable, sliced order
+  const uint16_t* X;
+  int64_t ldx;
+  const float* dst_scale;  // nullable
+  float* Y;
+  int64_t ldy;
+  int64_t n_dst, n_src, F;
+  int64_t n_slices;
+  float* planes;
+  int64_t ldp;
+  int64_t chunk_rows;
+  const int32_t* eid;
+  const void* keep;
+  int n_keep;
+  Epilogue ep;
+  bool full_width;
+  bool id_mult;
+};
+hipError_t spmm_sliced_bf16(const SlicedBf16Args& a, hipStream_t s);
+// out[r, :] = bf16_rne(scale[r] * X[r, :]) (scale nullable), one streaming pass; F, ldo multiples of 8, ldx of 4
+hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t n, int64_t F, uint16_t* out, int64_t ldo,
+                        hipStream_t s);
+
 // out[e] = cat(A[src[e]], B[dst[e]])   (dgmi_edge.hip)
 hipError_t gather_concat_f32(const int32_t* src, const int32_t* dst, int64_t E, const float* A,
                              int64_t lda, int64_t Fa, const float* B, int64_t ldb, int64_t Fb,

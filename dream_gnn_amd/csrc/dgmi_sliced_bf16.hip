@@ -1,0 +1,454 @@
+// dgmi_sliced_bf16.hip — the XCD-local CSR SpMM of dgmi_sliced.hip gathering from a bf16 copy of the feature table.
+//
+// What the gather kernel of dgmi_sliced.hip moves is nnz * 4F bytes of fp32 source rows; its rate (the L2 -> CU row-gather
+// rate) is spent.  Here the gathered operand — and only it — is bf16: a row is 2F bytes, the slice of a 100 000-source
+// table at F = 128 is 3.2 MB and fits an XCD's 4 MiB L2 at full width.  The table is made by ONE streaming pass
+// (rows_to_bf16_kernel) that also applies the source scale, in fp32, before the single round-to-nearest-even:
+//
+//   xb[j]  = bf16_rne(src_scale[j] * X[j])
+//   Y[i]   = dst_scale[i] * sum_{e: dst(e) = i} w_e * float(xb[src(e)])          (products, sums, planes, Y: fp32)
+//
+// Layout (segptr, id words, multiplicity bits 28..30, dropped flag in bit 31), row-boundary logic, touch-ahead blocks,
+// batches of 8 gathers, tree and plane order are those of spmm_sliced_vec4_kernel: the sum of a row is taken in exactly
+// the same order, so the result is bit-identical to the fp32 product of the upcast table whenever both run with the same
+// rows per lane group and row chunks.  A lane owns 8 columns (one 16-B load per gathered row), so a lane group is half as
+// wide as the fp32 kernel's for the same F.  No source-scale variant: the scale belongs to the conversion pass.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dgmi_kernels.h"
+#include "dgmi_segment.h"
+#include "dgmi_tuning.h"
+
+namespace dgmi {
+namespace {
+
+constexpr int64_t kColumnPassMinRows = 32768;  // as dgmi_sliced.hip
+constexpr int kRowsPerGroup = 8;
+constexpr int kTouchLead = 24;
+constexpr int kTouchGroup = 8;
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
+  // one streaming 16-B store (dgmi_sliced.hip): the planes are write-once / read-once
+  v4f t = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
+}
+
+// two fp32 -> one dword of two bf16, round-to-nearest-even (v_cvt_pk_bf16_f32); element 0 in the low half
+__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+  const v2f f = {lo, hi};
+  const v2bf b = __builtin_convertvector(f, v2bf);
+  return __builtin_bit_cast(uint32_t, b);
+}
+
+// out[r, :] = bf16_rne(scale[r] * X[r, :]); one thread per 8 columns: two 16-B loads, one 16-B store
+template <bool HAS_SCALE>
+__global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restrict__ X, int64_t ldx,
+                                                           const float* __restrict__ scale, int64_t n, int F8,
+                                                           uint16_t* __restrict__ out, int64_t ldo) {
+  const int64_t total = n * F8;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
+    const int64_t row = t / F8;
+    const int c = (int)(t - row * F8) * 8;
+    const float* src = X + row * ldx + c;
+    float4 a = ld4(src), b = ld4(src + 4);
+    if (HAS_SCALE) {
+      const float s = scale[row];
+      a.x *= s, a.y *= s, a.z *= s, a.w *= s;
+      b.x *= s, b.y *= s, b.z *= s, b.w *= s;
+    }
+    const v4u o = {pack_bf16(a.x, a.y), pack_bf16(a.z, a.w), pack_bf16(b.x, b.y), pack_bf16(b.z, b.w)};
+    *reinterpret_cast<v4u*>(out + row * ldo + c) = o;
+  }
+}
+
+// Source row `idx` of the bf16 table: this lane's 8 columns, one 16-B load.  OFF32: the table is < 4 GiB (see ld_row of
+// dgmi_sliced.hip).
+template <bool OFF32>
+__device__ __forceinline__ v4u ld_row8(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Xc, int idx, int64_t ldx,
+                                       uint32_t row_bytes, uint32_t col_bytes) {
+  if (OFF32) return *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
+  return *reinterpret_cast<const v4u*>(Xc + (int64_t)idx * ldx);
+}
+
+// bf16 -> fp32 is a shift (element 2k: the low half of dword k) or a mask (element 2k + 1): exact
+__device__ __forceinline__ float4 widen(uint32_t u0, uint32_t u1) {
+  return make_float4(__uint_as_float(u0 << 16), __uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 << 16),
+                     __uint_as_float(u1 & 0xffff0000u));
+}
+
+// One dword (2 columns) of a fast-path batch: widen, weight, the balanced tree of tree_sum (dgmi_segment.h) per column,
+// one add into the running sum.  Weighted, the fp32 kernel's `v *= w` + tree is contracted by the compiler into
+// fma(x[2k+1], w[2k+1], round(x[2k] * w[2k])) at the first tree level and plain adds above it; that arithmetic is spelled
+// out here (contraction off), so that the two kernels round alike: the bit-identity test holds both to it.
+template <bool WEIGHTED, int K>
+__device__ __forceinline__ void batch_pair(const v4u (&raw)[kUnroll], const float (&w)[kUnroll], float& acc0, float& acc1) {
+#pragma clang fp contract(off)
+  float lo[kUnroll / 2], hi[kUnroll / 2];
+#pragma unroll
+  for (int k = 0; k < kUnroll / 2; ++k) {
+    const uint32_t e = raw[2 * k][K], o = raw[2 * k + 1][K];
+    const float le = __uint_as_float(e << 16), he = __uint_as_float(e & 0xffff0000u);
+    const float lo_ = __uint_as_float(o << 16), ho = __uint_as_float(o & 0xffff0000u);
+    if (WEIGHTED) {
+      lo[k] = __builtin_fmaf(lo_, w[2 * k + 1], le * w[2 * k]);
+      hi[k] = __builtin_fmaf(ho, w[2 * k + 1], he * w[2 * k]);
+    } else {
+      lo[k] = le + lo_;
+      hi[k] = he + ho;
+    }
+  }
+  static_assert(kUnroll == 8, "the tree below is written for batches of 8");
+  acc0 += (lo[0] + lo[1]) + (lo[2] + lo[3]);
+  acc1 += (hi[0] + hi[1]) + (hi[2] + hi[3]);
+}
+
+// The gather of spmm_sliced_vec4_kernel (dgmi_sliced.hip) with 8 columns per lane: see there for the grid, the
+// touch-ahead blocks, KEEP and VALS.  Every float4 operation of that kernel is done twice here (columns 0..3 in `a`,
+// 4..7 in `b`), in the same order.  Built for five waves per SIMD (96 VGPRs) like that kernel's forms without a source scale;
+// a per-edge weight together with dropout on the fly or with 8-lane groups needs 100-109 VGPRs: four waves, no scratch.
+template <int LPR, int VALS, bool KEEP, bool OFF32>
+__global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR == 8)) ? 4 : 5) void spmm_sliced_bf16_kernel(
+    const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ vals,
+    const uint16_t* __restrict__ X, int64_t ldx, float* __restrict__ planes, int64_t ldp, int64_t n_dst, int64_t row_begin,
+    int64_t row_end, int F, int n_slices, const int32_t* __restrict__ eid, const KeepSeg* __restrict__ keep, int n_keep,
+    int touch_lead, int rows_per_group, int touch_group) {
+  constexpr int G = kWave / LPR;
+  const int R = rows_per_group;  // < LPR: a group's row boundaries live one per lane
+  constexpr bool HAS_VALS = VALS == 1;
+  constexpr bool MULT = VALS == 2;
+  constexpr bool WEIGHTED = HAS_VALS || MULT;
+  constexpr int kIdMask = MULT ? (int)kMultIdMask : 0x7fffffff;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x >> 6;
+  const int grp = lane / LPR, glane = lane % LPR, gbase = grp * LPR;
+  const int slice = (int)(blockIdx.x % (unsigned)n_slices);
+  int64_t block = blockIdx.x / (unsigned)n_slices;
+  if (touch_group > 0) {
+    // touch-ahead: every (touch_group + 1)-th block of a slice gathers nothing and touches the boundaries and id lines
+    // of the worker blocks touch_lead further on in the same slice (dgmi_sliced.hip); a hint, results never depend on it
+    const int64_t t = block / (touch_group + 1);
+    if (block % (touch_group + 1) == 0) {
+      __shared__ int range[2];
+      const int32_t* sp_s = segptr + (int64_t)slice * n_dst;
+      const int64_t rows_blk = (int64_t)kWavesPerBlock * G * R;
+      const int64_t r_first = row_begin + (t * touch_group + touch_lead) * rows_blk;
+      if (r_first >= row_end) return;  // block-uniform
+      const int64_t r_last = min(r_first + touch_group * rows_blk, row_end);
+      int keepalive = 0;
+      if (wave == 0) {
+        const int64_t rp = lane == 0 ? r_first : (lane == 1 ? r_last : r_first + (int64_t)(lane - 1) * 32);
+        if (rp <= r_last) {
+          const int v = sp_s[rp];
+          if (lane < 2) range[lane] = v;
+          keepalive = v;
+        }
+      }
+      __syncthreads();
+      const int e0 = range[0], e1 = range[1];
+      for (int64_t p = (int64_t)e0 + (int64_t)threadIdx.x * 32; p < e1; p += (int64_t)blockDim.x * 32) {
+        keepalive ^= indices[p];
+        if (HAS_VALS) keepalive ^= __float_as_int(vals[p]);
+        if (KEEP) keepalive ^= eid[p];
+      }
+      asm volatile("" ::"v"(keepalive));
+      return;
+    }
+    block -= t + 1;  // worker blocks are numbered without the touchers
+  }
+  const int64_t row0 = row_begin + ((block * kWavesPerBlock + wave) * G + grp) * R;
+  if (row0 >= row_end) return;  // whole group idle
+  const int nr = (int)(row0 + R <= row_end ? R : row_end - row0);
+  int col = ((int)blockIdx.y * LPR + glane) * 8;
+  const bool col_ok = col < F;  // F % 8 == 0: all 8 columns or none
+  if (!col_ok) col = 0;
+  const uint16_t* Xc = X + col;
+  const uint32_t row_bytes = (uint32_t)ldx * 2u, col_bytes = (uint32_t)col * 2u;
+  const int32_t* sp = segptr + (int64_t)slice * n_dst + row0;
+  float* prow = planes + ((int64_t)slice * (row_end - row_begin) + (row0 - row_begin)) * ldp + col;
+
+  const KeepPre first = first_seg<KEEP>(keep, n_keep);
+  const int my_b = sp[glane < nr ? glane : nr];  // lane k holds boundary k (k <= nr)
+  const int e_begin = __shfl(my_b, gbase, kWave);
+  const int e_end = __shfl(my_b, gbase + nr, kWave);
+  int r = 0;
+  int next_b = __shfl(my_b, gbase + 1, kWave);
+  float4 acc_a = make_float4(0.f, 0.f, 0.f, 0.f), acc_b = make_float4(0.f, 0.f, 0.f, 0.f);
+  int nxt_idx = 0;
+  float nxt_w = 0.f;
+  int last_row = -1;  // KEEP: the row this group gathered last (where a dropped edge's load is parked)
+  if (e_begin < e_end) {
+    const int q = e_begin + glane < e_end ? e_begin + glane : e_begin;
+    nxt_idx = fetch_id<KEEP>(indices, eid, first, keep, n_keep, q);
+    if (HAS_VALS) nxt_w = vals[q];
+  }
+  for (int base = e_begin; base < e_end; base += LPR) {
+    const int n = min(LPR, e_end - base);
+    const int my_idx = nxt_idx;
+    const float my_w = nxt_w;
+    if (base + LPR < e_end) {
+      const int nb = base + LPR;
+      const int q = nb + glane < e_end ? nb + glane : nb;
+      nxt_idx = fetch_id<KEEP>(indices, eid, first, keep, n_keep, q);
+      if (HAS_VALS) nxt_w = vals[q];
+    }
+    for (int j = 0; j < n; j += kUnroll) {
+      v4u raw[kUnroll];
+      float w[kUnroll];
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int e = j + u;  // < LPR
+        int idx = __shfl(my_idx, gbase + e, kWave);
+        if (HAS_VALS) w[u] = __shfl(my_w, gbase + e, kWave);
+        if (MULT) w[u] = (float)(((idx >> kMultShift) & kMultMax) + 1);  // the multiplicity arrived with the id
+        const bool dropped = KEEP && idx < 0;
+        if (KEEP) {
+          idx = dropped && last_row >= 0 ? last_row : idx & kIdMask;
+          last_row = idx;
+        } else if (MULT) {
+          idx &= kIdMask;
+        }
+        raw[u] = ld_row8<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
+        if (dropped) raw[u] = v4u{0u, 0u, 0u, 0u};  // a select, not 0 * x: Inf / NaN behind a dropped edge must not leak
+      }
+      // fast path (group-uniform): all 8 edges belong to the current row -> balanced tree, no per-edge boundary tests;
+      // dword by dword: 16 widened values live at a time, not 64
+      if (base + j + kUnroll <= next_b) {
+        batch_pair<WEIGHTED, 0>(raw, w, acc_a.x, acc_a.y);
+        __builtin_amdgcn_sched_barrier(0);  // one dword's 16 widened values at a time
+        batch_pair<WEIGHTED, 1>(raw, w, acc_a.z, acc_a.w);
+        __builtin_amdgcn_sched_barrier(0);
+        batch_pair<WEIGHTED, 2>(raw, w, acc_b.x, acc_b.y);
+        __builtin_amdgcn_sched_barrier(0);
+        batch_pair<WEIGHTED, 3>(raw, w, acc_b.z, acc_b.w);
+        continue;
+      }
+#pragma unroll
+      for (int u = 0; u < kUnroll; ++u) {
+        const int p = base + j + u;
+        if (p < e_end) {  // group-uniform
+          while (p >= next_b) {  // row(s) ended before this edge: emit them (empty rows emit zeros)
+            if (col_ok) {
+              store_plane_row(prow + (int64_t)r * ldp, acc_a);
+              store_plane_row(prow + (int64_t)r * ldp + 4, acc_b);
+            }
+            acc_a = acc_b = make_float4(0.f, 0.f, 0.f, 0.f);
+            ++r;
+            next_b = __shfl(my_b, gbase + r + 1, kWave);
+          }
+          const float4 va = widen(raw[u].x, raw[u].y), vb = widen(raw[u].z, raw[u].w);
+          if (WEIGHTED) {
+            acc_a.x = fmaf(w[u], va.x, acc_a.x);
+            acc_a.y = fmaf(w[u], va.y, acc_a.y);
+            acc_a.z = fmaf(w[u], va.z, acc_a.z);
+            acc_a.w = fmaf(w[u], va.w, acc_a.w);
+            acc_b.x = fmaf(w[u], vb.x, acc_b.x);
+            acc_b.y = fmaf(w[u], vb.y, acc_b.y);
+            acc_b.z = fmaf(w[u], vb.z, acc_b.z);
+            acc_b.w = fmaf(w[u], vb.w, acc_b.w);
+          } else {
+            acc_a.x += va.x;
+            acc_a.y += va.y;
+            acc_a.z += va.z;
+            acc_a.w += va.w;
+            acc_b.x += vb.x;
+            acc_b.y += vb.y;
+            acc_b.z += vb.z;
+            acc_b.w += vb.w;
+          }
+        }
+      }
+    }
+  }
+  for (; r < nr; ++r) {  // the last non-empty row, then any trailing empty rows
+    if (col_ok) {
+      store_plane_row(prow + (int64_t)r * ldp, acc_a);
+      store_plane_row(prow + (int64_t)r * ldp + 4, acc_b);
+    }
+    acc_a = acc_b = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// The plane reduce of dgmi_sliced.hip, restated here so that that file's instantiations stay what they are:
+// Y[row] = dst_scale[row] * (plane_0[row] + plane_1[row] + ...) in slice order; planes, dst_scale, Epilogue and Y are fp32.
+template <bool HAS_DS, int S>
+__global__ __launch_bounds__(256) void reduce_planes_kernel(const float* __restrict__ planes, int64_t ldp,
+                                                            int64_t rows, int F4, int n_slices,
+                                                            const float* __restrict__ dst_scale,
+                                                            float* __restrict__ Y, int64_t ldy, Epilogue ep) {
+  const int64_t total = rows * F4;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t plane_stride = rows * ldp;
+  const bool dense = (ldp == 4 * (int64_t)F4) && (ldy == ldp);  // element t of a plane is at offset 4t
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
+    int64_t row, poff, yoff;
+    if (dense) {
+      row = t / F4;
+      poff = yoff = 4 * t;
+    } else {
+      row = t / F4;
+      const int c = (int)(t - row * F4) * 4;
+      poff = row * ldp + c;
+      yoff = row * ldy + c;
+    }
+    const float* p = planes + poff;
+    float4 acc;
+    if (S > 0) {
+      float4 v[S > 0 ? S : 1];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p + s * plane_stride));
+        v[s] = make_float4(t.x, t.y, t.z, t.w);
+      }
+      acc = v[0];
+#pragma unroll
+      for (int s = 1; s < S; ++s) {
+        acc.x += v[s].x;
+        acc.y += v[s].y;
+        acc.z += v[s].z;
+        acc.w += v[s].w;
+      }
+    } else {
+      acc = *reinterpret_cast<const float4*>(p);
+      for (int s = 1; s < n_slices; ++s) {
+        const float4 v = *reinterpret_cast<const float4*>(p + s * plane_stride);
+        acc.x += v.x;
+        acc.y += v.y;
+        acc.z += v.z;
+        acc.w += v.w;
+      }
+    }
+    if (HAS_DS) {
+      const float d = dst_scale[row];
+      acc.x *= d;
+      acc.y *= d;
+      acc.z *= d;
+      acc.w *= d;
+    }
+    *reinterpret_cast<float4*>(Y + yoff) = epilogue4(ep, acc, row, (int)(yoff - row * ldy));
+  }
+}
+
+// pick_lpr (dgmi_kernels.h) on F / 8 lanes, widths 32 / 16 / 8: the widest tile whose last tile is >= 85 % used
+int pick_lpr_bf16(int64_t F) {
+  const int64_t f8 = (F + 7) / 8;
+  int best = 8;
+  double best_util = 0.0;
+  for (int lpr : {32, 16, 8}) {
+    const int64_t tiles = (f8 + lpr - 1) / lpr;
+    const double util = (double)f8 / (double)(tiles * lpr);
+    if (util >= 0.85) return lpr;
+    if (util > best_util + 1e-9) {
+      best_util = util;
+      best = lpr;
+    }
+  }
+  return best;
+}
+
+template <int LPR>
+hipError_t launch_sliced_bf16(const SlicedBf16Args& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
+  constexpr int G = kWave / LPR;
+  // rows per lane group, touch-ahead, 32-bit offsets: the rules and the Tuning knobs of launch_sliced (dgmi_sliced.hip)
+  const Tuning& tune = tuning();
+  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : kRowsPerGroup;
+  const int R = rows_req < 1 ? 1 : (rows_req < LPR ? rows_req : LPR - 1);
+  const int64_t per_block = (int64_t)kWavesPerBlock * G * R;
+  const int64_t blocks = (row_end - row_begin + per_block - 1) / per_block;
+  dim3 block(kWave * kWavesPerBlock);
+  const int key = (a.vals ? 2 : (a.id_mult ? 4 : 0)) | (a.n_keep > 0 ? 1 : 0);
+  const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * 2 < ((int64_t)1 << 32);
+  const int touch_lead = tune.sliced_touch_lead >= 0 ? tune.sliced_touch_lead : kTouchLead;
+  const int touch_group = touch_lead > 0 ? kTouchGroup : 0;
+  const int64_t touchers = touch_group > 0 ? (blocks + touch_group - 1) / touch_group : 0;
+  dim3 grid((unsigned)((blocks + touchers) * a.n_slices), (unsigned)((a.F + 8 * LPR - 1) / (8 * LPR)));
+#define DGMI_LAUNCH(V, K)                                                                                          \
+  do {                                                                                                             \
+    if (off32)                                                                                                     \
+      hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, true>), grid, block, 0, s, a.segptr, a.indices, a.vals, \
+                         a.X, a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices, a.eid, \
+                         static_cast<const KeepSeg*>(a.keep), a.n_keep, touch_lead, R, touch_group);                \
+    else                                                                                                           \
+      hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, false>), grid, block, 0, s, a.segptr, a.indices, a.vals, \
+                         a.X, a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices, a.eid, \
+                         static_cast<const KeepSeg*>(a.keep), a.n_keep, touch_lead, R, touch_group);                \
+  } while (0)
+  switch (key) {
+    case 0: DGMI_LAUNCH(0, false); break;
+    case 1: DGMI_LAUNCH(0, true); break;
+    case 2: DGMI_LAUNCH(1, false); break;
+    case 3: DGMI_LAUNCH(1, true); break;
+    case 4: DGMI_LAUNCH(2, false); break;
+    default: DGMI_LAUNCH(2, true); break;
+  }
+#undef DGMI_LAUNCH
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t n, int64_t F, uint16_t* out, int64_t ldo,
+                        hipStream_t s) {
+  if (n == 0 || F == 0) return hipSuccess;
+  const int F8 = (int)(F / 8);
+  int64_t blocks = (n * F8 + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  if (scale != nullptr)
+    hipLaunchKernelGGL(rows_to_bf16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, scale, n, F8, out, ldo);
+  else
+    hipLaunchKernelGGL(rows_to_bf16_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, X, ldx, scale, n, F8, out, ldo);
+  return hipGetLastError();
+}
+
+hipError_t spmm_sliced_bf16(const SlicedBf16Args& a, hipStream_t s) {
+  if (a.n_dst == 0 || a.F == 0) return hipSuccess;
+  const int F4 = (int)(a.F / 4);
+  const int64_t chunk = a.chunk_rows > 0 ? a.chunk_rows : a.n_dst;  // row chunks as spmm_sliced_f32
+  for (int64_t r0 = 0; r0 < a.n_dst; r0 += chunk) {
+    const int64_t r1 = r0 + chunk < a.n_dst ? r0 + chunk : a.n_dst;
+    hipError_t err;
+    // Lane-group width = column tile of 8 * LPR columns.  The column-pass rule of spmm_sliced_f32 on the bytes of a bf16
+    // slice: half the width when the slice one XCD gathers from (n_src / n_slices rows x 16 LPR bytes) exceeds its 4 MiB
+    // L2 — at 2 bytes per column a 100 000-source table at F = 128 (3.2 MB per slice) stays at full width.
+    const int forced_lpr = tuning().sliced_lpr;
+    int lpr = pick_lpr_bf16(a.F);
+    if (lpr >= 32 && !a.full_width && a.n_keep == 0 && a.n_dst >= kColumnPassMinRows) {
+      const int64_t width = 16 * (int64_t)lpr < 2 * a.F ? 16 * (int64_t)lpr : 2 * a.F;
+      const int64_t slice_bytes = (a.n_src + a.n_slices - 1) / a.n_slices * width;
+      if (slice_bytes > (4 << 20)) lpr /= 2;
+    }
+    if (forced_lpr == 8 || forced_lpr == 16 || forced_lpr == 32) lpr = forced_lpr;
+    switch (lpr) {
+      case 8: err = launch_sliced_bf16<8>(a, r0, r1, s); break;
+      case 16: err = launch_sliced_bf16<16>(a, r0, r1, s); break;
+      default: err = launch_sliced_bf16<32>(a, r0, r1, s); break;
+    }
+    if (err != hipSuccess) return err;
+    int64_t blocks = ((r1 - r0) * F4 + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    const float* ds = a.dst_scale ? a.dst_scale + r0 : nullptr;
+    float* y = a.Y + r0 * a.ldy;
+    Epilogue ep = a.ep;  // rows of this chunk start at r0
+    if (ep.mask != nullptr) ep.mask += r0 * ep.ldm;
+#define DGMI_REDUCE(D, S)                                                                               \
+  hipLaunchKernelGGL((reduce_planes_kernel<D, S>), dim3((unsigned)blocks), dim3(256), 0, s, a.planes, a.ldp, \
+                     r1 - r0, F4, (int)a.n_slices, ds, y, a.ldy, ep)
+    if (a.n_slices == 8) {
+      if (ds) DGMI_REDUCE(true, 8); else DGMI_REDUCE(false, 8);
+    } else {
+      if (ds) DGMI_REDUCE(true, 0); else DGMI_REDUCE(false, 0);
+    }
+#undef DGMI_REDUCE
+    err = hipGetLastError();
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
+}  // namespace dgmi

@@ -26,6 +26,7 @@
 
 #include "dgmi.h"
 #include "dgmi_above.h"
+#include "dgmi_bf16.h"
 #include "dgmi_pairs.h"
 #include "dgmi_rank.h"
 
@@ -755,6 +756,68 @@ void spmm_sliced_out(const Tensor& segptr, const Tensor& indices, const OptTenso
                   column_passes, id_mult);
 }
 
+// bf16_rne(diag(scale) X) in one streaming pass: the gather table of spmm_sliced_bf16_raw (include/dgmi_bf16.h)
+Tensor rows_to_bf16(const Tensor& X, const OptTensor& scale) {
+  Dense x = dense16_of(X, "X");
+  TORCH_CHECK(x.F % 8 == 0, "rows_to_bf16: X must have a multiple of 8 columns (16-B rows of bf16), got ", x.F);
+  check_opt(scale, at::kFloat, x.rows, "scale", x.t);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.t.device());
+  Tensor out = at::empty({x.rows, x.F}, x.t.options().dtype(at::kBFloat16));
+  check_status(dgmi_rows_to_bf16(x.t.data_ptr<float>(), x.ld, (const float*)optptr(scale), x.rows, x.F,
+                                 reinterpret_cast<uint16_t*>(out.data_ptr()), x.F > 0 ? x.F : 8, stream_of(x.t)),
+               "dgmi_rows_to_bf16");
+  return out;
+}
+
+// the XCD-local product gathering from a bf16 table; accumulation, planes and output fp32 (dgmi_spmm_sliced_bf16)
+Tensor spmm_sliced_bf16_impl(const Tensor& segptr, const Tensor& indices, const OptTensor& vals, const OptTensor& eid,
+                             const OptTensor& keep, const Tensor& X, const OptTensor& dst_scale, int64_t n_dst, int64_t n_slices,
+                             const OptTensor& out, int64_t act, double slope, const OptTensor& out_mask, double mask_scale,
+                             int64_t column_passes, int64_t id_mult) {
+  check(segptr, at::kInt, 1, "segptr", segptr);
+  check(indices, at::kInt, 1, "indices", segptr);
+  TORCH_CHECK(segptr.numel() == n_slices * n_dst + 1, "segptr has ", segptr.numel(), " entries, expected n_slices * n_dst + 1");
+  check_dev(X, "X");
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 && X.dim() == 2, "X must be a 2-D bfloat16 tensor");
+  TORCH_CHECK(X.device() == segptr.device(), "X and the graph are on different devices");
+  TORCH_CHECK(X.size(1) % 8 == 0, "the bf16 gather needs a multiple of 8 columns (16-B rows), got ", X.size(1));
+  Tensor x = X;  // rows contiguous, 16-B aligned: a row-strided view is consumed in place, anything else is copied
+  if (X.stride(1) != 1 || (X.size(0) > 1 && (X.stride(0) < X.size(1) || X.stride(0) % 8 != 0)) ||
+      (reinterpret_cast<uintptr_t>(X.data_ptr()) & 15))
+    x = X.clone(at::MemoryFormat::Contiguous);
+  const int64_t rows = x.size(0), F = x.size(1), ldx = rows > 1 ? x.stride(0) : (F > 0 ? F : 8);
+  const int64_t nnz = indices.numel();
+  check_opt(vals, at::kFloat, nnz, "vals", segptr);
+  check_opt(dst_scale, at::kFloat, n_dst, "dst_scale", segptr);
+  const Keep k = keep_of(eid, keep, nnz, segptr);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(segptr.device());
+  Tensor y = out_of(out, n_dst, F, segptr);
+  const Epi e = epi_of(act, slope, out_mask, mask_scale, n_dst, F, segptr);
+  const size_t pbytes = dgmi_spmm_sliced_planes_bytes(n_dst, (int32_t)n_slices, F);
+  Tensor planes = scratch(segptr, pbytes, kPlanes);
+  check_status(dgmi_spmm_sliced_bf16(segptr.data_ptr<int32_t>(), indices.data_ptr<int32_t>(), (const float*)optptr(vals), k.eid,
+                                     k.table, k.n, reinterpret_cast<const uint16_t*>(x.data_ptr()), ldx,
+                                     (const float*)optptr(dst_scale), y.data_ptr<float>(), F, n_dst, rows, F, (int32_t)n_slices,
+                                     (int32_t)column_passes, (int32_t)id_mult, planes.data_ptr(), pbytes, e.act, e.slope, e.mask,
+                                     e.ldm, e.mscale, stream_of(segptr)), "dgmi_spmm_sliced_bf16");
+  return y;
+}
+
+Tensor spmm_sliced_bf16_new(const Tensor& segptr, const Tensor& indices, const OptTensor& vals, const OptTensor& eid,
+                            const OptTensor& keep, const Tensor& X, const OptTensor& ds, int64_t n_dst, int64_t n_slices,
+                            int64_t act, double slope, const OptTensor& out_mask, double mask_scale, int64_t column_passes,
+                            int64_t id_mult) {
+  return spmm_sliced_bf16_impl(segptr, indices, vals, eid, keep, X, ds, n_dst, n_slices, c10::nullopt, act, slope, out_mask,
+                               mask_scale, column_passes, id_mult);
+}
+void spmm_sliced_bf16_out(const Tensor& segptr, const Tensor& indices, const OptTensor& vals, const OptTensor& eid,
+                          const OptTensor& keep, const Tensor& X, const OptTensor& ds, int64_t n_dst, int64_t n_slices, Tensor out,
+                          int64_t act, double slope, const OptTensor& out_mask, double mask_scale, int64_t column_passes,
+                          int64_t id_mult) {
+  spmm_sliced_bf16_impl(segptr, indices, vals, eid, keep, X, ds, n_dst, n_slices, out, act, slope, out_mask, mask_scale,
+                        column_passes, id_mult);
+}
+
 // ---------------------------------------------------------------------------------------------
 // dreamgnn_mi::spmm_csr — the functional op of §8(b), with autograd w.r.t. X.
 Tensor spmm_csr_forward(const Tensor& indptr, const Tensor& indices, const OptTensor& vals, const Tensor& X,
@@ -822,6 +885,13 @@ TORCH_LIBRARY(dreamgnn_mi, m) {
   m.def("spmm_sliced_out(Tensor segptr, Tensor indices, Tensor? vals, Tensor? eid, Tensor? keep, Tensor X, Tensor? src_scale, "
         "Tensor? dst_scale, int n_dst, int n_slices, Tensor(a!) out, int act=0, float slope=0., Tensor? out_mask=None, "
         "float mask_scale=1., int column_passes=0, int id_mult=0) -> ()");
+  m.def("rows_to_bf16(Tensor X, Tensor? scale=None) -> Tensor");
+  m.def("spmm_sliced_bf16_raw(Tensor segptr, Tensor indices, Tensor? vals, Tensor? eid, Tensor? keep, Tensor X, Tensor? dst_scale, "
+        "int n_dst, int n_slices, int act=0, float slope=0., Tensor? out_mask=None, float mask_scale=1., int column_passes=0, "
+        "int id_mult=0) -> Tensor");
+  m.def("spmm_sliced_bf16_out(Tensor segptr, Tensor indices, Tensor? vals, Tensor? eid, Tensor? keep, Tensor X, Tensor? dst_scale, "
+        "int n_dst, int n_slices, Tensor(a!) out, int act=0, float slope=0., Tensor? out_mask=None, float mask_scale=1., "
+        "int column_passes=0, int id_mult=0) -> ()");
   m.def("epilogue_backward(Tensor dY, Tensor Y, Tensor? mask, int act, float slope, float mask_scale) -> Tensor");
   m.def("knn_cosine_topk(Tensor Xn, int k) -> Tensor");
   m.def("pair_mlp_topk(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_drug, Tensor? known_dis, "
@@ -856,6 +926,9 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
   m.impl("spmm_csr_out", spmm_csr_out);
   m.impl("spmm_sliced_raw", spmm_sliced_new);
   m.impl("spmm_sliced_out", spmm_sliced_out);
+  m.impl("rows_to_bf16", rows_to_bf16);
+  m.impl("spmm_sliced_bf16_raw", spmm_sliced_bf16_new);
+  m.impl("spmm_sliced_bf16_out", spmm_sliced_bf16_out);
   m.impl("epilogue_backward", epilogue_backward);
   m.impl("knn_cosine_topk", knn_cosine_topk);
   m.impl("pair_mlp_topk", pair_mlp_topk);

@@ -16,6 +16,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import threading
 from typing import Optional, Tuple
 
 import torch
@@ -28,6 +29,47 @@ _NULLCTX = contextlib.nullcontext()
 #: output epilogue of a product: (act, slope, out_mask, mask_scale) — act 0 none / 1 leaky-relu(slope);
 #: out_mask: 0/1 keep mask of the output (dropout), multiplied in with mask_scale = 1 / (1 - p)
 _NO_EPI = (0, 0.0, None, 1.0)
+
+# Precision of the GATHERED operand of the XCD-local products.  float32: the table as it is; bfloat16: a
+# bf16 copy made by one streaming pass (`rows_to_bf16`, source scale folded in, one round-to-nearest-even) — sums, planes
+# and outputs stay float32.  A product asks with `gather_dtype=`; calls that pass none take the thread's default.
+_GATHER_DTYPES = (torch.float32, torch.bfloat16)
+_gather_default = threading.local()
+
+
+def _check_gather_dtype(dtype):
+    if dtype is not None and dtype not in _GATHER_DTYPES:
+        raise ValueError("gather_dtype must be None, torch.float32 or torch.bfloat16, got %r" % (dtype,))
+    return dtype
+
+
+def _resolve_gather_dtype(dtype):
+    """``dtype`` if given, else the default of :func:`gather_precision` on this thread, else float32."""
+    if _check_gather_dtype(dtype) is not None:
+        return dtype
+    return getattr(_gather_default, "dtype", None) or torch.float32
+
+
+@contextlib.contextmanager
+def gather_precision(dtype):
+    """Default ``gather_dtype`` of the products issued by THIS thread inside the block, for calls that pass none: the
+    drop-in modules keep the reference's signatures, so this is how a model opts in —
+    ``with gather_precision(torch.bfloat16): loss = forward_loss(...)``.  Blocks nest; ``None`` restores float32.  A
+    product records the dtype it ran with, so its backward uses the same one wherever it runs."""
+    _check_gather_dtype(dtype)
+    prev = getattr(_gather_default, "dtype", None)
+    _gather_default.dtype = dtype
+    try:
+        yield
+    finally:
+        _gather_default.dtype = prev
+
+
+def rows_to_bf16(X: torch.Tensor, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bf16_rne(diag(scale) X)`` in one streaming pass (``dgmi_rows_to_bf16``): the product in float32, rounded once;
+    bitwise ``(scale[:, None] * X).to(torch.bfloat16)``.  ``X.shape[1]`` must be a multiple of 8."""
+    _require_device(X, scale)
+    return _T.rows_to_bf16(X, None if scale is None else scale.reshape(-1).contiguous())
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -181,6 +223,16 @@ def _sliced_ok(X, out) -> bool:
     return out is None or (out.is_contiguous() and out.data_ptr() % 16 == 0)
 
 
+def _sliced_bf16_ok(X, out) -> bool:
+    """The same for a product that gathers bf16: a float32 ``X`` as :func:`_sliced_ok` (so that a refused request takes
+    exactly today's path), a bfloat16 ``X`` with 16-B aligned rows."""
+    if X.dtype == torch.float32:
+        return _sliced_ok(X, out)
+    if X.dtype != torch.bfloat16 or X.stride(1) != 1 or X.stride(0) % 8 != 0 or X.data_ptr() % 16 != 0:
+        return False
+    return out is None or (out.is_contiguous() and out.data_ptr() % 16 == 0)
+
+
 class SlicedCSR:
     """Source-sliced CSR for the XCD-local SpMM (``dgmi_csr_sliced_from_coo_i32``): edges sorted
     by (slice(src), row); ``segptr`` has ``n_slices * n_dst + 1`` entries."""
@@ -237,17 +289,42 @@ class SlicedCSR:
         return table_bytes <= 6 * int(self.indices.shape[0]) * passes
 
     def spmm(self, X, src_scale=None, dst_scale=None, out=None, vals=_DEFAULT, keep=None, epi=None, full_width=False,
-             indices=None, id_mult=None):
+             indices=None, id_mult=None, gather_dtype=None):
         """``vals`` (in sliced order, see ``eid``) overrides the values given at construction; ``indices`` with
         ``id_mult=True``: id words carrying integer edge multiplicities (bits 28..30 = m - 1; then ``vals`` must be None);
         ``keep``: subset descriptions applied through ``eid`` (edge dropout on the fly); ``epi``: output
         epilogue (act, slope, out_mask, mask_scale) applied by the plane-reduce kernel; ``full_width``:
-        never sweep the columns in two half-width passes (``column_passes = 1`` of the C ABI)."""
+        never sweep the columns in two half-width passes (``column_passes = 1`` of the C ABI).
+
+        A bfloat16 ``X`` is gathered as it is (``dgmi_spmm_sliced_bf16``: float32 sums, planes and output), without a
+        ``src_scale`` — the scale belongs to the conversion.  ``gather_dtype=torch.bfloat16`` with a float32 ``X`` makes
+        that table first, ``rows_to_bf16(X, src_scale)``, and gathers from it.  This method reads the keyword only, never
+        the default of :func:`gather_precision`."""
         vals = self.vals if vals is SlicedCSR._DEFAULT else vals
+        _check_gather_dtype(gather_dtype)
+        if X.dtype == torch.bfloat16 and src_scale is not None:
+            raise RuntimeError("a bfloat16 X cannot take a src_scale: the scale is applied in float32 BEFORE the one rounding "
+                               "to bf16 — pass the float32 table (with gather_dtype=torch.bfloat16) or rows_to_bf16(X, src_scale)")
         if not X.is_cuda or X.device != self.segptr.device:
             _require_device(self.segptr, X)
         if X.dim() == 2 and X.shape[0] != self.n_src:
             raise RuntimeError("X has %d rows, the graph has %d source nodes" % (X.shape[0], self.n_src))
+        if X.dtype == torch.bfloat16 or gather_dtype == torch.bfloat16:
+            if X.dim() != 2 or X.shape[1] % 8 != 0:
+                raise RuntimeError("the bf16 gather needs a 2-D table with a multiple of 8 columns, got %s" % (tuple(X.shape),))
+            if X.dtype != torch.bfloat16:
+                if X.dtype != torch.float32:
+                    raise RuntimeError("X must be float32 or bfloat16, got %s" % X.dtype)
+                X = _T.rows_to_bf16(X, None if src_scale is None else src_scale.reshape(-1).contiguous())
+            id_mult = self.id_mult if id_mult is None else bool(id_mult)
+            args = (self.segptr, self.indices if indices is None else indices, vals, self.eid if keep is not None else None,
+                    None if keep is None else _prep_keep(keep), X, None if dst_scale is None else dst_scale.reshape(-1),
+                    self.n_dst, self.n_slices)
+            epi = epi or _NO_EPI
+            if out is None:
+                return _T.spmm_sliced_bf16_raw(*args, *epi, 1 if full_width else 0, int(id_mult))
+            _T.spmm_sliced_bf16_out(*args, out, *epi, 1 if full_width else 0, int(id_mult))
+            return out
         if src_scale is not None and X.dim() == 2 and self._prescale_pays(X.shape[0] * X.shape[1] * 4, keep is not None or full_width):
             # diag(src_scale) X as ONE streaming pass, then the un-scaled gather: inside the kernel the scale is a
             # random 4-byte load per edge (and per column pass) — one more cache-line request beside the row's four —
@@ -771,13 +848,91 @@ class CSRGraph:
                             None if row_scale is None else row_scale.reshape(-1), out, plan, n_rows, n_cols, 0, 0,
                             eid if self._keep is not None else None, self._keep, epi)
 
-    def spmm(self, X, src_scale=None, dst_scale=None, out=None, epi=None):
+    # -- bf16 gather ------------------------------------------------------------------
+    def _bf16_gather_reason(self, F: int, transposed: bool) -> Optional[str]:
+        """None when a product of width ``F`` gathers bf16 on request, else why it does not.  The form rule
+        (``_use_sliced``) keeps judging the FLOAT32 table bytes: its thresholds were fitted to 4-byte rows."""
+        S = self._S
+        n_rows, n_cols, regular = (S.n_src, S.n_dst, S.regular_t) if transposed else (S.n_dst, S.n_src, S.regular)
+        if F % 8 != 0:
+            return "F = %d is not a multiple of 8 (a lane loads 8 bf16 columns)" % F
+        if (bool(regular) and self._few_long_rows(F, n_rows, n_cols)) or not self._use_sliced(F, n_rows, n_cols, regular):
+            return ("a %d x %d product at F = %d does not take the plain XCD-local form (it runs the planned, wave-per-row "
+                    "or split kernels, which gather float32 only)" % (n_rows, n_cols, F))
+        return None
+
+    def takes_bf16_gather(self, F: int, transposed: bool = False) -> bool:
+        """Whether ``spmm`` (``transposed=True``: ``spmm_t``) honours ``gather_dtype=torch.bfloat16`` at width ``F``:
+        the product takes the plain XCD-local form and ``F % 8 == 0``.  Otherwise a float32 ``X`` silently takes the
+        float32 path and a bfloat16 ``X`` raises."""
+        S = self._S
+        if (S.regular_t if transposed else S.regular) is None:
+            self._decide_regular(torch.empty((0, int(F)), dtype=torch.float32, device=self.device), transposed)
+        return self._bf16_gather_reason(int(F), transposed) is None
+
+    def _bf16_request(self, X, out, gather_dtype, transposed: bool) -> bool:
+        """True: run :meth:`_spmm_bf16`.  False: today's float32 path.  Raises for a bfloat16 ``X`` that cannot be gathered."""
+        if X.dtype != torch.bfloat16 and _resolve_gather_dtype(gather_dtype) != torch.bfloat16:
+            return False
+        if X.dim() != 2:
+            reason = "X is not 2-D"
+        else:
+            reason = self._bf16_gather_reason(X.shape[1], transposed)
+            if reason is None and not _sliced_bf16_ok(X, out):
+                reason = "the rows of X (or out) are not contiguous and 16-byte aligned"
+        if reason is not None and X.dtype == torch.bfloat16:
+            raise RuntimeError("a bfloat16 X is only taken by the XCD-local bf16 gather, and %s: pass the float32 table" % reason)
+        return reason is None
+
+    def _spmm_bf16(self, X, gathered_scale, out_scale, out, epi, transposed: bool):
+        """The plain XCD-local product with a bf16 gather: ``gathered_scale`` multiplies the gathered rows (folded into
+        the conversion of a float32 ``X``), ``out_scale`` the output rows (applied by the plane reduce)."""
+        S = self._S
+        if transposed:
+            name = "sliced_t"
+            if S.sliced_t is None:
+                indptr_t, indices_t, eid_t, _ = self._t_struct()
+                S.sliced_t = SlicedCSR.from_csr(indptr_t, indices_t, eid_t, S.n_src, S.n_dst)
+            layout = S.sliced_t
+        else:
+            name = "sliced"
+            if S.sliced is None:
+                S.sliced = SlicedCSR.from_csr(S.indptr, S.indices, S.eid, S.n_dst, S.n_src)
+            layout = S.sliced
+        mult = self._mult_ids(name, layout)
+        if mult is not None:  # the scale of `scale x multiplicity` values lands on the output rows or on the gathered rows
+            if (mult[0] == "row") != transposed:
+                out_scale = self._fold(mult[1], out_scale)
+            else:
+                gathered_scale = self._fold(mult[1], gathered_scale)
+        if X.dtype == torch.bfloat16:
+            if gathered_scale is not None:
+                raise RuntimeError("a bfloat16 X cannot take a scale on the gathered rows (src_scale, or the row scale of this "
+                                   "graph's `scale x multiplicity` values): it is applied in float32 before the one rounding — "
+                                   "pass the float32 table")
+            gd = None
+        else:
+            gd = torch.bfloat16
+        c = self._compacted(name, layout, mult)
+        if c is not None:
+            return c.spmm(X, gathered_scale, out_scale, out, epi=epi, gather_dtype=gd)
+        if mult is not None:
+            return layout.spmm(X, gathered_scale, out_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2],
+                               id_mult=True, gather_dtype=gd)
+        return layout.spmm(X, gathered_scale, out_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi,
+                           gather_dtype=gd)
+
+    def spmm(self, X, src_scale=None, dst_scale=None, out=None, epi=None, gather_dtype=None):
         """``diag(dst_scale) A diag(src_scale) X`` (no autograd).  Picks the XCD-local sliced kernel when the
         feature table is a few L2s large and the graph is regular, else the planned kernel.  ``epi``: output epilogue
-        (act, slope, out_mask, mask_scale), fused into the kernel that writes the result."""
+        (act, slope, out_mask, mask_scale), fused into the kernel that writes the result.  ``gather_dtype`` (default:
+        :func:`gather_precision`'s): ``torch.bfloat16`` gathers from a bf16 copy of ``diag(src_scale) X`` where
+        :meth:`takes_bf16_gather` holds, and is the float32 product elsewhere."""
         S = self._S
         if S.regular is None:
             self._decide_regular(X, False)
+        if self._bf16_request(X, out, gather_dtype, False):
+            return self._spmm_bf16(X, src_scale, dst_scale, out, epi, False)
         long_rows = X.dim() == 2 and bool(S.regular) and self._few_long_rows(X.shape[1], S.n_dst, S.n_src)
         if (X.dim() == 2 and not long_rows and self._use_sliced(X.shape[1], S.n_dst, S.n_src, S.regular)
                 and _sliced_ok(X, out)):
@@ -807,12 +962,15 @@ class CSRGraph:
         return self._run(S.indptr, S.indices, self.vals, self._plan_if_needed(S.plan, S.max_deg), S.n_dst, S.n_src, X,
                          src_scale, dst_scale, out, S.eid, epi)
 
-    def spmm_t(self, dY, src_scale=None, dst_scale=None, out=None):
-        """``diag(src_scale) A^T diag(dst_scale) dY`` — the backward of :meth:`spmm`."""
+    def spmm_t(self, dY, src_scale=None, dst_scale=None, out=None, gather_dtype=None):
+        """``diag(src_scale) A^T diag(dst_scale) dY`` — the backward of :meth:`spmm`.  With a bf16 gather ``dst_scale``
+        is folded into the conversion of ``dY`` and ``src_scale`` is applied by the plane reduce."""
         S = self._S
         indptr_t, indices_t, eid_t, plan_t = self._t_struct()
         if S.regular_t is None:  # one-time readback of the reversed graph's maximum degree, when it can matter
             self._decide_regular(dY, True)
+        if self._bf16_request(dY, out, gather_dtype, True):
+            return self._spmm_bf16(dY, dst_scale, src_scale, out, None, True)
         long_rows = dY.dim() == 2 and bool(S.regular_t) and self._few_long_rows(dY.shape[1], S.n_src, S.n_dst)
         if (dY.dim() == 2 and not long_rows and self._use_sliced(dY.shape[1], S.n_src, S.n_dst, S.regular_t)
                 and _sliced_ok(dY, out)):
@@ -845,10 +1003,10 @@ class CSRGraph:
 
 class _SpMM(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X, g: CSRGraph, src_scale, dst_scale):
-        ctx.g = g
+    def forward(ctx, X, g: CSRGraph, src_scale, dst_scale, gather_dtype=torch.float32):
+        ctx.g, ctx.gather_dtype = g, gather_dtype  # the backward may run outside a gather_precision block
         ctx.save_for_backward(src_scale, dst_scale)
-        return g.spmm(X, src_scale, dst_scale)
+        return g.spmm(X, src_scale, dst_scale, gather_dtype=gather_dtype)
 
     @staticmethod
     def backward(ctx, dY):
@@ -861,8 +1019,8 @@ class _SpMM(torch.autograd.Function):
             # the planned kernel would lose.)
             if not dY.is_contiguous():
                 dY = dY.contiguous()
-            dX = ctx.g.spmm_t(dY, src_scale, dst_scale)
-        return dX, None, None, None
+            dX = ctx.g.spmm_t(dY, src_scale, dst_scale, gather_dtype=ctx.gather_dtype)
+        return dX, None, None, None, None
 
 
 class _SpMMEpilogue(torch.autograd.Function):
@@ -870,9 +1028,9 @@ class _SpMMEpilogue(torch.autograd.Function):
     applied by the kernel that writes the product (f3, reference layers.py:134-138)."""
 
     @staticmethod
-    def forward(ctx, X, g: CSRGraph, src_scale, dst_scale, act, slope, mask, mask_scale):
-        y = g.spmm(X, src_scale, dst_scale, epi=(act, slope, mask, mask_scale))
-        ctx.g, ctx.epi = g, (act, slope, mask_scale)
+    def forward(ctx, X, g: CSRGraph, src_scale, dst_scale, act, slope, mask, mask_scale, gather_dtype=torch.float32):
+        y = g.spmm(X, src_scale, dst_scale, epi=(act, slope, mask, mask_scale), gather_dtype=gather_dtype)
+        ctx.g, ctx.epi, ctx.gather_dtype = g, (act, slope, mask_scale), gather_dtype
         ctx.save_for_backward(src_scale, dst_scale, y, mask)
         return y
 
@@ -883,8 +1041,8 @@ class _SpMMEpilogue(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[0]:
             g_pre = epilogue_backward(dY.contiguous(), y, mask, act, slope, mask_scale)
-            dX = ctx.g.spmm_t(g_pre, src_scale, dst_scale)
-        return dX, None, None, None, None, None, None, None
+            dX = ctx.g.spmm_t(g_pre, src_scale, dst_scale, gather_dtype=ctx.gather_dtype)
+        return dX, None, None, None, None, None, None, None, None
 
 
 def colsum_rows_(feat_ext, coef, n: int, R: int, i0: int):
@@ -909,24 +1067,26 @@ def epilogue_backward(dY, Y, mask, act, slope, mask_scale):
 
 
 def spmm_csr_act_dropout(g: CSRGraph, X, src_scale=None, dst_scale=None, act: int = 0, slope: float = 0.0,
-                         mask: Optional[torch.Tensor] = None, mask_scale: float = 1.0) -> torch.Tensor:
+                         mask: Optional[torch.Tensor] = None, mask_scale: float = 1.0, gather_dtype=None) -> torch.Tensor:
     """:func:`spmm_csr` followed by ``leaky_relu`` (``act=1``) and a dropout keep ``mask`` (0/1 floats of
     the output's shape, scaled by ``mask_scale``), both inside the product's last kernel."""
     if src_scale is not None and src_scale.requires_grad or dst_scale is not None and dst_scale.requires_grad:
         raise RuntimeError("spmm_csr: gradients w.r.t. the diagonal scales are not part of the path")
-    return _SpMMEpilogue.apply(X, g, src_scale, dst_scale, act, slope, mask, mask_scale)
+    return _SpMMEpilogue.apply(X, g, src_scale, dst_scale, act, slope, mask, mask_scale, _resolve_gather_dtype(gather_dtype))
 
 
 def spmm_csr(g: CSRGraph, X: torch.Tensor, src_scale: Optional[torch.Tensor] = None,
-             dst_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+             dst_scale: Optional[torch.Tensor] = None, gather_dtype=None) -> torch.Tensor:
     """``Y = diag(dst_scale) · A · diag(src_scale) · X`` with autograd w.r.t. ``X`` only.
 
     The reference needs no other gradient: adjacency values are constants (utils.py:24-27,
     augmentation.py:124) and ``ci``/``cj`` are non-learnable node data (data_loader.py:487-488).
+    ``gather_dtype`` (default: :func:`gather_precision`'s): see :meth:`CSRGraph.spmm`; the backward,
+    ``dX = diag(ss) A^T diag(ds) dY``, gathers ``dY`` in the same precision wherever it runs.
     """
     if src_scale is not None and src_scale.requires_grad or dst_scale is not None and dst_scale.requires_grad:
         raise RuntimeError("spmm_csr: gradients w.r.t. the diagonal scales are not part of the path")
-    return _SpMM.apply(X, g, src_scale, dst_scale)
+    return _SpMM.apply(X, g, src_scale, dst_scale, _resolve_gather_dtype(gather_dtype))
 
 
 # ---------------------------------------------------------------------------------------------
