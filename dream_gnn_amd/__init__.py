@@ -18,7 +18,8 @@ The package holds only what the path needs:
 * ``predict``  — ``top_novel_pairs``: the k best novel drug-disease pairs of a trained ``Net`` (train.py:26-151);
   ``top_novel_per_disease`` / ``top_novel_per_drug``: the k best novel candidates of every disease / drug;
   ``novel_pairs_above`` / ``count_novel_pairs_above`` / ``top_novel_pairs_deep``: every novel pair at or above a score
-  cut, their exact number, and the k best for k beyond the on-chip limit.
+  cut, their exact number, and the k best for k beyond the on-chip limit; ``score_pairs`` / ``rank_pairs``: the score
+  of given pairs and each pair's filtered rank among the candidates of its row (hits@k, MRR).
 
 There is no CPU fallback: every op raises if ``libdgmi.so`` is missing or a tensor is
 not on a HIP device.
@@ -26,9 +27,10 @@ not on a HIP device.
 from . import _lib  # noqa: F401  (fails loudly if the extension is not built)
 from .ops import (CSRGraph, EdgePairs, SlicedCSR, SpmmPlan, csr_from_coo, gather_add, gather_concat,  # noqa: F401
                   gather_precision, random_subset_mask, spmm_csr)
-from .predict import (NovelLists, NovelPairs, count_novel_pairs_above, novel_pairs_above, top_novel_pairs,  # noqa: F401
-                      top_novel_pairs_deep, top_novel_per_disease, top_novel_per_drug)
+from .predict import (NovelLists, NovelPairs, PairRanks, count_novel_pairs_above, novel_pairs_above, rank_pairs,  # noqa: F401
+                      score_pairs, top_novel_pairs, top_novel_pairs_deep, top_novel_per_disease, top_novel_per_drug)
 
 __all__ = ["CSRGraph", "EdgePairs", "SlicedCSR", "SpmmPlan", "csr_from_coo", "gather_add", "gather_concat",
            "gather_precision", "random_subset_mask", "spmm_csr", "NovelPairs", "top_novel_pairs", "NovelLists", "top_novel_per_disease",
-           "top_novel_per_drug", "novel_pairs_above", "count_novel_pairs_above", "top_novel_pairs_deep"]
+           "top_novel_per_drug", "novel_pairs_above", "count_novel_pairs_above", "top_novel_pairs_deep", "PairRanks", "score_pairs",
+           "rank_pairs"]

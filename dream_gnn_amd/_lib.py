@@ -109,6 +109,17 @@ BF16_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); mirrors include/dgmi_given.h (a sixth table, for the same reason).
+GIVEN_SIGNATURES = {
+    "dgmi_pair_rank_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
+    "dgmi_pair_mlp_score_list_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "dgmi_pair_mlp_rank_list_f32": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                   ctypes.c_size_t, _vp]),
+}
+
+
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
 
@@ -120,8 +131,9 @@ def _load() -> ctypes.CDLL:
             "or `make -C dream_gnn_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
-                              + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the five headers declare
+                              + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
+                              + list(GIVEN_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the six headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

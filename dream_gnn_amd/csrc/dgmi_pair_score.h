@@ -112,6 +112,33 @@ __device__ __forceinline__ void score_two(const float* pa, const float* pb, cons
   lb = (sb + __shfl_xor(sb, 32)) + d.bias3;
 }
 
+// Logit of ONE stream row per call, two accumulators: score_two's row a, step for step (the same MFMA order per
+// accumulator, the same epilogue order), so the bits are the same.  pa may differ from lane column to lane column: the
+// operand B = relu(pa[k] + q[k]) is the lane's own, and column j's logit depends on column j's B alone.
+__device__ __forceinline__ void score_one(const float* pa, const float (&q)[kH1 / 2], const PairDecoder& d, float& la) {
+  floatx16 c00, c01;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) c00[v] = c01[v] = 0.f;
+#pragma unroll
+  for (int s4 = 0; s4 < 16; ++s4) {
+    const float4 xa = *reinterpret_cast<const float4*>(pa + 4 * s4);
+    const float va[4] = {xa.x, xa.y, xa.z, xa.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int s = 4 * s4 + u;
+      const float ba = relu_nan(va[u] + q[s]);
+      c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(d.wa[s], ba, c00, 0, 0, 0);
+      c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(d.wb[s], ba, c01, 0, 0, 0);
+    }
+  }
+  float sa = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sa = fmaf(d.ew[0][r], relu_nan(c00[r] + d.eb[0][r]), sa);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sa = fmaf(d.ew[1][r], relu_nan(c01[r] + d.eb[1][r]), sa);
+  la = (sa + __shfl_xor(sa, 32)) + d.bias3;
+}
+
 // known[(s, l)] -> bit l & 31 of word s * nwords + l / 32 (s: the streamed id, l: the lane id); an id outside its
 // range sets info[1] and is skipped.  Vector atomics only.
 __global__ __launch_bounds__(256) void known_bitmap_kernel(const int32_t* __restrict__ ks, const int32_t* __restrict__ kl,

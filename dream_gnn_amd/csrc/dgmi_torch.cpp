@@ -27,6 +27,7 @@
 #include "dgmi.h"
 #include "dgmi_above.h"
 #include "dgmi_bf16.h"
+#include "dgmi_given.h"
 #include "dgmi_pairs.h"
 #include "dgmi_rank.h"
 
@@ -551,6 +552,94 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_row_topk(const Tensor& X, co
   return {out_cand, out_logit, out_count, info};
 }
 
+// the decoder MLP on GIVEN (query, candidate) pairs (dgmi_pairs_given.hip).  rank = false: logits only; rank = true: also
+// above / total, the pair's position among the candidates of its query row that are not known (n_pairs x n_cand scores).
+// info = [a listed id is out of range, a known id is out of range]; a pair out of range gets NaN / -1 / -1 and the others
+// their results.  int64 ids are clamped into [-1, INT32_MAX] on the device, as in pair_mlp_topk; nothing here synchronises.
+struct GivenOut {
+  Tensor logit, above, total, info;
+};
+
+GivenOut pair_mlp_given(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2, const Tensor& w3, const Tensor& b3,
+                        const Tensor& pair_query, const Tensor& pair_cand, const OptTensor& known_query,
+                        const OptTensor& known_cand, bool rank) {
+  Dense x = dense16_of(X, "X"), c = dense16_of(C, "C");
+  TORCH_CHECK(x.F == 128 && c.F == 128, "X and C must have 128 columns (the decoder's lin1 width), got ", x.F, " and ", c.F);
+  check(W2, at::kFloat, 2, "W2", X);
+  TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
+  check(b2, at::kFloat, 1, "b2", X);
+  check(w3, at::kFloat, 1, "w3", X);
+  check(b3, at::kFloat, 1, "b3", X);
+  TORCH_CHECK(b2.numel() == 64 && w3.numel() == 64 && b3.numel() == 1, "b2 / w3 / b3 must have 64 / 64 / 1 entries");
+  const bool has_known = known_query.has_value() && known_query->defined();
+  TORCH_CHECK(has_known == (known_cand.has_value() && known_cand->defined()), "known_query and known_cand go together");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.t.device());
+  auto ids_ok = [&](const Tensor& t, const char* what) {
+    check_dev(t, what);
+    TORCH_CHECK(t.dim() == 1 && (t.scalar_type() == at::kInt || t.scalar_type() == at::kLong) && t.device() == X.device(), what,
+                " must be 1-D int32 / int64 tensors on ", X.device().str());
+  };
+  auto i32 = [](const Tensor& t) {
+    return t.scalar_type() == at::kInt ? t.contiguous() : t.clamp(-1, (int64_t)INT32_MAX).to(at::kInt).contiguous();
+  };
+  ids_ok(pair_query, "pair ids");
+  ids_ok(pair_cand, "pair ids");
+  TORCH_CHECK(pair_query.numel() == pair_cand.numel(), "pair_query / pair_cand length mismatch");
+  Tensor pq = i32(pair_query), pc = i32(pair_cand), kq, kc;
+  if (has_known) {
+    ids_ok(*known_query, "known ids");
+    ids_ok(*known_cand, "known ids");
+    TORCH_CHECK(known_query->numel() == known_cand->numel(), "known_query / known_cand length mismatch");
+    kq = i32(*known_query);
+    kc = i32(*known_cand);
+  }
+  const int64_t n_pairs = pq.numel(), n_known = has_known ? kq.numel() : 0;
+  auto opts = x.t.options();
+  GivenOut o;
+  o.logit = at::empty({n_pairs}, opts.dtype(at::kFloat));
+  o.above = at::empty({rank ? n_pairs : 0}, opts.dtype(at::kInt));
+  o.total = at::empty({rank ? n_pairs : 0}, opts.dtype(at::kInt));
+  o.info = at::zeros({2}, opts.dtype(at::kInt));
+  if (n_pairs == 0) return o;
+  Tensor W2c = contiguous16(W2), b2c = b2.contiguous(), w3c = w3.contiguous(), b3c = b3.contiguous();
+  TORCH_CHECK(rows_16b_aligned(x.t, x.ld) && rows_16b_aligned(c.t, c.ld), "X and C rows must be 16-B aligned");
+  if (!rank) {
+    check_status(dgmi_pair_mlp_score_list_f32(x.t.data_ptr<float>(), x.ld, x.rows, c.t.data_ptr<float>(), c.ld, c.rows, 128, 64,
+                                              W2c.data_ptr<float>(), b2c.data_ptr<float>(), w3c.data_ptr<float>(),
+                                              b3c.data_ptr<float>(), pq.data_ptr<int32_t>(), pc.data_ptr<int32_t>(), n_pairs,
+                                              o.logit.data_ptr<float>(), o.info.data_ptr<int32_t>(), stream_of(x.t)),
+                 "dgmi_pair_mlp_score_list_f32");
+    return o;
+  }
+  // per call, from the caching allocator, as pair_mlp_topk
+  const size_t wbytes = dgmi_pair_rank_workspace_bytes(x.rows, c.rows, n_pairs);
+  Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
+  check_status(dgmi_pair_mlp_rank_list_f32(x.t.data_ptr<float>(), x.ld, x.rows, c.t.data_ptr<float>(), c.ld, c.rows, 128, 64,
+                                           W2c.data_ptr<float>(), b2c.data_ptr<float>(), w3c.data_ptr<float>(),
+                                           b3c.data_ptr<float>(), pq.data_ptr<int32_t>(), pc.data_ptr<int32_t>(), n_pairs,
+                                           has_known ? kq.data_ptr<int32_t>() : nullptr,
+                                           has_known ? kc.data_ptr<int32_t>() : nullptr, n_known, o.logit.data_ptr<float>(),
+                                           o.above.data_ptr<int32_t>(), o.total.data_ptr<int32_t>(), o.info.data_ptr<int32_t>(),
+                                           ws.data_ptr(), (size_t)ws.numel(), stream_of(x.t)),
+               "dgmi_pair_mlp_rank_list_f32");
+  return o;
+}
+
+std::tuple<Tensor, Tensor> pair_mlp_score_list(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2,
+                                               const Tensor& w3, const Tensor& b3, const Tensor& pair_query,
+                                               const Tensor& pair_cand) {
+  GivenOut o = pair_mlp_given(X, C, W2, b2, w3, b3, pair_query, pair_cand, c10::nullopt, c10::nullopt, false);
+  return {o.logit, o.info};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_rank_list(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2,
+                                                              const Tensor& w3, const Tensor& b3, const Tensor& pair_query,
+                                                              const Tensor& pair_cand, const OptTensor& known_query,
+                                                              const OptTensor& known_cand) {
+  GivenOut o = pair_mlp_given(X, C, W2, b2, w3, b3, pair_query, pair_cand, known_query, known_cand, true);
+  return {o.logit, o.above, o.total, o.info};
+}
+
 // every novel pair whose decoder logit reaches `min_logit` (dgmi_pairs_above.hip), appended in scheduling order to the
 // caller's record tensors (capacity = their length; 0 = count only): returns count = [the exact int64 number of
 // qualifying pairs, which may exceed the capacity] and info = [0, out-of-range flag].  Nothing is written past the
@@ -898,6 +987,10 @@ TORCH_LIBRARY(dreamgnn_mi, m) {
         "int k) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("pair_mlp_row_topk(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_query, "
         "Tensor? known_cand, int k) -> (Tensor cand, Tensor logit, Tensor count, Tensor info)");
+  m.def("pair_mlp_score_list(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor pair_query, "
+        "Tensor pair_cand) -> (Tensor logit, Tensor info)");
+  m.def("pair_mlp_rank_list(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor pair_query, "
+        "Tensor pair_cand, Tensor? known_query, Tensor? known_cand) -> (Tensor logit, Tensor above, Tensor total, Tensor info)");
   m.def("pair_mlp_emit(Tensor P, Tensor Q, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor? known_drug, Tensor? known_dis, "
         "float min_logit, Tensor(a!) out_drug, Tensor(b!) out_dis, Tensor(c!) out_logit) -> (Tensor count, Tensor info)");
   m.def("pair_records_sort(Tensor(a!) drug, Tensor(b!) dis, Tensor(c!) logit, int n) -> ()");
@@ -933,6 +1026,8 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
   m.impl("knn_cosine_topk", knn_cosine_topk);
   m.impl("pair_mlp_topk", pair_mlp_topk);
   m.impl("pair_mlp_row_topk", pair_mlp_row_topk);
+  m.impl("pair_mlp_score_list", pair_mlp_score_list);
+  m.impl("pair_mlp_rank_list", pair_mlp_rank_list);
   m.impl("pair_mlp_emit", pair_mlp_emit);
   m.impl("pair_records_sort", pair_records_sort);
   m.impl("scale_rows", scale_rows);

@@ -303,6 +303,68 @@ class MLPDecoder(nn.Module):
                 break
         return drug[:k], dis[:k], logit[:k]
 
+    def score_pairs(self, drug_feat, dis_feat, drug_ids, dis_ids):
+        """The eval-mode logit of every listed pair ``(drug_ids[e], dis_ids[e])`` (``ops.pair_mlp_score_list``): an fp32
+        device tensor in the caller's order, every logit bit-identical to the one :meth:`top_pairs`,
+        :meth:`top_pairs_per_row` and :meth:`pairs_above` return for the pair (``lin1`` is split as there; this is not
+        the arithmetic of :meth:`forward`).  Duplicates are allowed.  ``ValueError`` for id lists of different length or
+        of float / bool type, before anything touches the device; ``RuntimeError`` for an id out of range."""
+        drug_ids, dis_ids = pair_ids(drug_ids, dis_ids)
+        P, Q = self._split_lin1(drug_feat, dis_feat)
+        return ops.pair_mlp_score_list(P, Q, *self._tail(), drug_ids.to(P.device), dis_ids.to(P.device))
+
+    def rank_pairs(self, drug_feat, dis_feat, drug_ids, dis_ids, by="disease", known=None):
+        """Where every listed pair stands among the candidates of its row (``ops.pair_mlp_rank_list``): ``(logit, above,
+        total)`` device tensors in the caller's order.  ``by="disease"``: the query is the pair's disease and the
+        candidates are all drugs (the filtered rank of a held-out drug for its disease); ``by="drug"``: the mirror.
+        ``total`` counts the other candidates of the row whose pair is not in ``known = (drug_ids, disease_ids)``,
+        ``above`` those of them that rank before the listed pair (logit descending, ties by candidate id ascending, NaN
+        last): ``above + 1`` is the rank among ``total + 1``.  The listed pair never counts itself, whether it is in
+        ``known`` changes nothing, and duplicates get equal results.  The logits are those of :meth:`score_pairs`, so a
+        pair that :meth:`top_pairs_per_row` lists at position ``r`` of its row has ``above == r``.
+
+        Every listed pair scans its whole row: ``n_pairs x n_cand`` scores.  Only the distinct listed query rows are
+        given to the kernel, so the known-pair bitmap is ``n_cand x ceil(n_distinct / 32)`` words.  Argument errors as
+        in :meth:`score_pairs`, and ``ValueError`` for a bad ``by``."""
+        if by not in ("disease", "drug"):
+            raise ValueError('by must be "disease" or "drug", got %r' % (by,))
+        drug_ids, dis_ids = pair_ids(drug_ids, dis_ids)
+        P, Q = self._split_lin1(drug_feat, dis_feat)
+        dev = P.device
+        X, C = (Q, P) if by == "disease" else (P, Q)
+        pq, pc = (dis_ids, drug_ids) if by == "disease" else (drug_ids, dis_ids)
+        pq, pc = pq.to(dev), pc.to(dev)
+        n_query, n_cand = int(X.shape[0]), int(C.shape[0])
+        # the distinct listed rows become the query side; an id out of range stays -1 and is flagged by the kernel
+        q_ok = (pq >= 0) & (pq < n_query)
+        rows = torch.unique(pq[q_ok])
+        pos = torch.full((max(n_query, 1),), -1, dtype=torch.long, device=dev)
+        pos[rows] = torch.arange(rows.numel(), device=dev)
+        pq_new = torch.where(q_ok, pos[pq.clamp(0, max(n_query - 1, 0))], torch.full_like(pq, -1))
+        kq = kc = None
+        if known is not None:
+            kd, ks = known
+            kq, kc = (ks, kd) if by == "disease" else (kd, ks)
+            kq, kc = _remap_known(kq.to(dev).long(), kc.to(dev).long(), rows, n_query, n_cand)
+        return ops.pair_mlp_rank_list(X.index_select(0, rows), C, *self._tail(), pq_new, pc, kq, kc)
+
+
+def pair_ids(drug_ids, dis_ids):
+    """The two id lists of a pair list as 1-D int64 tensors (on the device they came on); ``ValueError`` for float,
+    complex or bool ids, more than one dimension or different lengths."""
+    out = []
+    for name, ids in (("drug_ids", drug_ids), ("disease_ids", dis_ids)):
+        t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+        if t.numel() == 0 and t.dim() == 1 and not isinstance(ids, (torch.Tensor, np.ndarray)):
+            t = t.long()  # an empty Python list has no dtype of its own
+        if t.dim() != 1 or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("%s must be a 1-D list of integer ids, got %s of shape %s" % (name, t.dtype, tuple(t.shape)))
+        out.append(t.detach().long())
+    if out[0].numel() != out[1].numel():
+        raise ValueError("drug / disease id lists differ in length: %d vs %d" % (out[0].numel(), out[1].numel()))
+    return out[0], out[1]
+
+
 def query_rows(rows, n_query: int):
     """``rows`` as a CPU int64 tensor of unique query ids in ``[0, n_query)``, or None; ``ValueError`` otherwise."""
     if rows is None:

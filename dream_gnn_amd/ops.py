@@ -1375,6 +1375,62 @@ def pair_mlp_count_above(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2:
     """How many pairs :func:`pair_mlp_above` would list at this cut, without storing any (capacity 0): exact, no limit."""
     return _pair_emit(P, Q, W2, b2, w3, b3, known_drug, known_dis, min_logit, 0)[3]
 
+
+# ---------------------------------------------------------------------------------------------
+# given pairs — the logit of a listed pair and its filtered position in its row (hits@k, MRR)
+# ---------------------------------------------------------------------------------------------
+def _pair_list(pair_query, pair_cand):
+    """The two id lists of a pair list, checked on the host: 1-D integer tensors of equal length (``ValueError``)."""
+    for name, t in (("pair_query", pair_query), ("pair_cand", pair_cand)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s must be a 1-D int32 / int64 tensor of ids" % name)
+    if pair_query.numel() != pair_cand.numel():
+        raise ValueError("pair id lists differ in length: %d vs %d" % (pair_query.numel(), pair_cand.numel()))
+
+
+def pair_mlp_score_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                        b3: torch.Tensor, pair_query: torch.Tensor, pair_cand: torch.Tensor) -> torch.Tensor:
+    """``logit = b3 + w3 . relu(W2 relu(X[q] + C[c]) + b2)`` of every listed pair ``(q, c) = (pair_query[e],
+    pair_cand[e])`` (``dgmi_pair_mlp_score_list_f32``): fp32 on the device, in the caller's order, every logit
+    bit-identical to the one :func:`pair_mlp_topk`, :func:`pair_mlp_row_topk` and :func:`pair_mlp_above` return for the
+    pair.  Duplicates are allowed.  The only host sync is reading the flag.  Raises ``ValueError`` for id lists that
+    are not 1-D integer tensors of equal length and ``RuntimeError`` when a listed id is out of range."""
+    _pair_list(pair_query, pair_cand)
+    _require_device(X, C, W2, b2, w3, b3, pair_query, pair_cand)
+    logit, info = _T.pair_mlp_score_list(X, C, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), pair_query, pair_cand)
+    if int(info[0]):
+        raise RuntimeError("pair_mlp_score_list: a listed (query, candidate) id is outside [0, %d) x [0, %d)"
+                           % (X.shape[0], C.shape[0]))
+    return logit
+
+
+def pair_mlp_rank_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
+                       b3: torch.Tensor, pair_query: torch.Tensor, pair_cand: torch.Tensor,
+                       known_query: Optional[torch.Tensor] = None,
+                       known_cand: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(logit, above, total)`` of every listed pair ``(q, c)`` (``dgmi_pair_mlp_rank_list_f32``): the logit of
+    :func:`pair_mlp_score_list`, and over the candidates ``c' != c`` with ``(q, c')`` not in ``(known_query,
+    known_cand)``: ``total``, how many there are, and ``above``, how many of them rank before ``(q, c)`` in the order of
+    :func:`pair_mlp_row_topk` (logit descending, ties by candidate id ascending, NaN last).  ``above + 1`` is the pair's
+    filtered rank among ``total + 1``.  The listed pair never counts itself, and whether it is in the known list changes
+    nothing; duplicates get equal results.  int32 ``above`` / ``total`` on the device, in the caller's order.
+
+    Cost: every listed pair scans its whole row, ``n_pairs x n_cand`` scores.  The only host sync is reading the
+    flags.  Raises ``ValueError`` as :func:`pair_mlp_score_list` and ``RuntimeError`` when a listed or a known id is
+    out of range."""
+    _pair_list(pair_query, pair_cand)
+    _require_device(X, C, W2, b2, w3, b3, pair_query, pair_cand, known_query, known_cand)
+    logit, above, total, info = _T.pair_mlp_rank_list(X, C, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), pair_query,
+                                                      pair_cand, known_query, known_cand)
+    bad_pair, bad_known = (int(v) for v in info.tolist())
+    if bad_pair:
+        raise RuntimeError("pair_mlp_rank_list: a listed (query, candidate) id is outside [0, %d) x [0, %d)"
+                           % (X.shape[0], C.shape[0]))
+    if bad_known:
+        raise RuntimeError("pair_mlp_rank_list: a known (query, candidate) id is outside [0, %d) x [0, %d)"
+                           % (X.shape[0], C.shape[0]))
+    return logit, above, total
+
 # ---------------------------------------------------------------------------------------------
 # (D3) edge-dropout selection — augmentation.py:48-52, 114-118
 # ---------------------------------------------------------------------------------------------

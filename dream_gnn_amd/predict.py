@@ -21,6 +21,12 @@ to that row: logit descending, ties by candidate id ascending, NaN last.
 or above a cut, and how many there are), and ``top_novel_pairs_deep`` ranks beyond the on-chip limit (``k`` up to 2**20):
 one streaming HIP kernel over the same scorer emits the qualifying pairs with an exact count, a device sort orders them
 (``MLPDecoder.pairs_above`` / ``top_pairs_deep``, ``csrc/dgmi_pairs_above.hip``).  Same order, same logit bits.
+
+``score_pairs`` / ``rank_pairs`` answer the reverse question: here is a pair, how does the model score it and where
+does it stand among the candidates of its row.  One HIP kernel scores the listed pairs, a second streams every
+candidate of each pair's row through the same scorer and only counts (``MLPDecoder.score_pairs`` / ``rank_pairs``,
+``csrc/dgmi_pairs_given.hip``).  Same logit bits, same order, so a rank agrees with the pair's position in
+``top_novel_per_disease`` / ``top_novel_per_drug``; ``PairRanks`` turns the ranks into hits@k and MRR.
 """
 from __future__ import annotations
 
@@ -30,7 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .model import query_rows
+from .model import pair_ids, query_rows
 
 #: the largest ``k`` the on-chip top-k takes; there is no other path inside :func:`top_novel_pairs` (for a deeper
 #: list see :func:`top_novel_pairs_deep`, for a list by score :func:`novel_pairs_above`)
@@ -279,3 +285,83 @@ def top_novel_pairs_deep(net, batch, known, k: int) -> NovelPairs:
         raise ValueError("k must be in 1..%d, got %d" % (DEEP_MAX_K, k))
     kn = _known_of(batch, known)
     return _novel_pairs(*_with_embedding(net, batch, lambda hd, hs: net.decoder.top_pairs_deep(hd, hs, k, kn)))
+
+
+@dataclass
+class PairRanks:
+    """Given pairs and where each stands in its row, CPU tensors in the caller's order: int64 ``drug_id`` /
+    ``disease_id``, fp32 ``logit`` and ``score = sigmoid(logit)``, int64 ``rank`` (1 is the best: one more than the
+    number of other novel candidates of the row that rank before the pair) and int64 ``n_candidates`` (the length of
+    the list the pair is ranked in, itself included).  ``by`` names the query side: ``"disease"`` ranks the pair's drug
+    among all drugs for its disease, ``"drug"`` the pair's disease among all diseases for its drug."""
+
+    by: str
+    drug_id: torch.Tensor
+    disease_id: torch.Tensor
+    logit: torch.Tensor
+    score: torch.Tensor
+    rank: torch.Tensor
+    n_candidates: torch.Tensor
+
+    def __len__(self) -> int:
+        return int(self.drug_id.numel())
+
+    def hits_at(self, k: int) -> float:
+        """The fraction of the listed pairs with ``rank <= k`` (NaN for an empty list)."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1, got %d" % k)
+        return float((self.rank <= k).double().mean()) if len(self) else float("nan")
+
+    def mrr(self) -> float:
+        """The mean reciprocal rank of the listed pairs (NaN for an empty list)."""
+        return float((1.0 / self.rank.double()).mean()) if len(self) else float("nan")
+
+    def to_frame(self, drug_names=None):
+        """A pandas DataFrame, one line per listed pair in the caller's order: ``drug_id, disease_id, score, rank,
+        n_candidates`` and, when ``drug_names`` (indexable by drug id) is given, ``drug_name``."""
+        import pandas as pd
+
+        df = pd.DataFrame({"drug_id": self.drug_id.numpy(), "disease_id": self.disease_id.numpy(),
+                           "score": self.score.numpy(), "rank": self.rank.numpy(),
+                           "n_candidates": self.n_candidates.numpy()})
+        if drug_names is not None:
+            names = list(drug_names)
+            df["drug_name"] = [names[i] for i in df["drug_id"]]
+        return df
+
+
+def score_pairs(net, batch, drug_ids, disease_ids) -> NovelPairs:
+    """How ``net`` scores the listed pairs ``(drug_ids[e], disease_ids[e])``, eval mode: a hand-picked candidate list.
+    ``batch`` as in :func:`top_novel_pairs`.  Returned in the CALLER'S order, not sorted; duplicates are allowed.  Every
+    logit has the bits the ranking functions of this module return for the pair.  Validates the id lists (equal
+    length, integers) before the model runs; an id out of range raises ``RuntimeError``.  The encoder runs once under
+    ``no_grad`` and the training flag is restored."""
+    drug_ids, disease_ids = pair_ids(drug_ids, disease_ids)
+    logit = _with_embedding(net, batch, lambda hd, hs: net.decoder.score_pairs(hd, hs, drug_ids, disease_ids))
+    return _novel_pairs(drug_ids, disease_ids, logit)
+
+
+def rank_pairs(net, batch, drug_ids, disease_ids, known, by: str = "disease") -> PairRanks:
+    """The filtered rank of every listed pair among the candidates of its row, eval mode: the evaluation protocol for
+    held-out indications.  ``by="disease"``: pair ``(d, s)`` is ranked among all drugs ``d'`` for disease ``s`` with
+    ``(d', s)`` not in ``known``; ``by="drug"``: among all diseases for drug ``d``.  ``batch`` and ``known`` as in
+    :func:`top_novel_pairs` (``known`` is normally the whole association matrix, held-out positives included).
+
+    The listed pair never counts itself and is ranked whether or not it is in ``known``; the other known pairs of its
+    row are left out.  Order within a row as everywhere in this module: logit descending, ties by candidate id
+    ascending, NaN last, so a pair at position ``r`` (from 0) of its row in :func:`top_novel_per_disease` has rank
+    ``r + 1``.  Duplicate listed pairs get equal results.  Returned in the caller's order.
+
+    Every listed pair scans its whole row (``n_pairs x n_candidates`` scores).  Validates the id lists, ``known`` and
+    ``by`` before the model runs; an id out of range raises ``RuntimeError``.  The encoder runs once under ``no_grad``
+    and the training flag is restored."""
+    if by not in ("disease", "drug"):
+        raise ValueError('by must be "disease" or "drug", got %r' % (by,))
+    drug_ids, disease_ids = pair_ids(drug_ids, disease_ids)
+    kn = _known_of(batch, known)
+    logit, above, total = _with_embedding(
+        net, batch, lambda hd, hs: net.decoder.rank_pairs(hd, hs, drug_ids, disease_ids, by, kn))
+    logit = logit.cpu()
+    return PairRanks(by, drug_ids.cpu(), disease_ids.cpu(), logit, torch.sigmoid(logit), above.cpu().long() + 1,
+                     total.cpu().long() + 1)
