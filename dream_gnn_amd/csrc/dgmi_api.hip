@@ -290,14 +290,14 @@ DGMI_API size_t dgmi_spmm_sliced_planes_bytes(int64_t n_dst, int32_t n_slices, i
   return b < 16 ? 16 : b;
 }
 
-DGMI_API int dgmi_spmm_sliced_f32(const int32_t* segptr, const int32_t* indices, const float* vals,
-                                  const int32_t* eid, const uint32_t* keep, int32_t n_keep,
-                                  const float* X, int64_t ldx, const float* src_scale,
-                                  const float* dst_scale, float* Y, int64_t ldy, int64_t n_dst,
-                                  int64_t n_src, int64_t F, int32_t n_slices, int32_t column_passes,
-                                  int32_t id_multiplicity, void* planes,
-                                  size_t planes_bytes, int32_t act, float act_slope, const float* out_mask,
-                                  int64_t ld_mask, float out_mask_scale, dgmi_stream_t stream) {
+// Argument checks and the launch of both XCD-local products: `x_bytes` per element of the gathered table X (4: fp32,
+// 2: bf16), F and ldx multiples of the 16 / x_bytes columns a lane loads at once.
+static int spmm_sliced(const int32_t* segptr, const int32_t* indices, const float* vals, const int32_t* eid, const uint32_t* keep,
+                       int32_t n_keep, const void* X, int x_bytes, int64_t ldx, const float* src_scale, const float* dst_scale,
+                       float* Y, int64_t ldy, int64_t n_dst, int64_t n_src, int64_t F, int32_t n_slices, int32_t column_passes,
+                       int32_t id_multiplicity, void* planes, size_t planes_bytes, int32_t act, float act_slope,
+                       const float* out_mask, int64_t ld_mask, float out_mask_scale, dgmi_stream_t stream) {
+  const int cols = 16 / x_bytes;
   if (n_dst < 0 || n_src < 0 || F < 0 || n_slices < 1 || n_slices > 64 || !keep_args_ok(eid, keep, n_keep) ||
       !epilogue_ok(act, out_mask, ld_mask, F) || column_passes < 0 || column_passes > 1 || id_multiplicity < 0 ||
       id_multiplicity > 1)
@@ -308,16 +308,29 @@ DGMI_API int dgmi_spmm_sliced_f32(const int32_t* segptr, const int32_t* indices,
   if (n_dst == 0 || F == 0) return DGMI_OK;
   if (segptr == nullptr || Y == nullptr || planes == nullptr) return DGMI_ERR_INVALID_ARG;
   if (X == nullptr && n_src > 0) return DGMI_ERR_INVALID_ARG;
-  if (ldx < F || ldy < F || F % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0) return DGMI_ERR_INVALID_ARG;
+  if (ldx < F || ldy < F || F % cols != 0 || ldx % cols != 0 || ldy % 4 != 0) return DGMI_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
       (reinterpret_cast<uintptr_t>(planes) & 15))
     return DGMI_ERR_INVALID_ARG;
-  if (static_cast<const void*>(X) == static_cast<const void*>(Y)) return DGMI_ERR_INVALID_ARG;
+  if (X == static_cast<const void*>(Y)) return DGMI_ERR_INVALID_ARG;
   if (planes_bytes < dgmi_spmm_sliced_planes_bytes(n_dst, n_slices, F)) return DGMI_ERR_WORKSPACE;
-  dgmi::SlicedArgs a{segptr, indices, vals, X, ldx, src_scale, dst_scale, Y, ldy, n_dst, n_src, F, n_slices,
+  dgmi::SlicedArgs a{segptr, indices, vals, X, x_bytes, ldx, src_scale, dst_scale, Y, ldy, n_dst, n_src, F, n_slices,
                      static_cast<float*>(planes), F, sliced_chunk_rows(n_dst, n_slices, F), eid, keep, n_keep,
                      {act, act_slope, out_mask, ld_mask, out_mask_scale}, column_passes == 1, id_multiplicity == 1};
-  return from_hip(dgmi::spmm_sliced_f32(a, as_stream(stream)));
+  return from_hip(x_bytes == 4 ? dgmi::spmm_sliced_f32(a, as_stream(stream)) : dgmi::spmm_sliced_bf16(a, as_stream(stream)));
+}
+
+DGMI_API int dgmi_spmm_sliced_f32(const int32_t* segptr, const int32_t* indices, const float* vals,
+                                  const int32_t* eid, const uint32_t* keep, int32_t n_keep,
+                                  const float* X, int64_t ldx, const float* src_scale,
+                                  const float* dst_scale, float* Y, int64_t ldy, int64_t n_dst,
+                                  int64_t n_src, int64_t F, int32_t n_slices, int32_t column_passes,
+                                  int32_t id_multiplicity, void* planes,
+                                  size_t planes_bytes, int32_t act, float act_slope, const float* out_mask,
+                                  int64_t ld_mask, float out_mask_scale, dgmi_stream_t stream) {
+  return spmm_sliced(segptr, indices, vals, eid, keep, n_keep, X, 4, ldx, src_scale, dst_scale, Y, ldy, n_dst, n_src, F,
+                     n_slices, column_passes, id_multiplicity, planes, planes_bytes, act, act_slope, out_mask, ld_mask,
+                     out_mask_scale, stream);
 }
 
 DGMI_API int dgmi_rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t n, int64_t F, uint16_t* out, int64_t ldo,
@@ -337,26 +350,9 @@ DGMI_API int dgmi_spmm_sliced_bf16(const int32_t* segptr, const int32_t* indices
                                    int32_t n_slices, int32_t column_passes, int32_t id_multiplicity, void* planes,
                                    size_t planes_bytes, int32_t act, float act_slope, const float* out_mask,
                                    int64_t ld_mask, float out_mask_scale, dgmi_stream_t stream) {
-  if (n_dst < 0 || n_src < 0 || F < 0 || n_slices < 1 || n_slices > 64 || !keep_args_ok(eid, keep, n_keep) ||
-      !epilogue_ok(act, out_mask, ld_mask, F) || column_passes < 0 || column_passes > 1 || id_multiplicity < 0 ||
-      id_multiplicity > 1)
-    return DGMI_ERR_INVALID_ARG;
-  if (id_multiplicity == 1 && (vals != nullptr || n_src > (int64_t)dgmi::kMultIdMask + 1)) return DGMI_ERR_INVALID_ARG;
-  if (out_mask != nullptr && (ld_mask % 4 != 0 || (reinterpret_cast<uintptr_t>(out_mask) & 15))) return DGMI_ERR_INVALID_ARG;
-  if (n_dst >= INT32_MAX || n_src >= INT32_MAX || F > INT32_MAX) return DGMI_ERR_TOO_LARGE;
-  if (n_dst == 0 || F == 0) return DGMI_OK;
-  if (segptr == nullptr || Y == nullptr || planes == nullptr) return DGMI_ERR_INVALID_ARG;
-  if (X == nullptr && n_src > 0) return DGMI_ERR_INVALID_ARG;
-  if (ldx < F || ldy < F || F % 8 != 0 || ldx % 8 != 0 || ldy % 4 != 0) return DGMI_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15) ||
-      (reinterpret_cast<uintptr_t>(planes) & 15))
-    return DGMI_ERR_INVALID_ARG;
-  if (static_cast<const void*>(X) == static_cast<const void*>(Y)) return DGMI_ERR_INVALID_ARG;
-  if (planes_bytes < dgmi_spmm_sliced_planes_bytes(n_dst, n_slices, F)) return DGMI_ERR_WORKSPACE;
-  dgmi::SlicedBf16Args a{segptr, indices, vals, X, ldx, dst_scale, Y, ldy, n_dst, n_src, F, n_slices,
-                         static_cast<float*>(planes), F, sliced_chunk_rows(n_dst, n_slices, F), eid, keep, n_keep,
-                         {act, act_slope, out_mask, ld_mask, out_mask_scale}, column_passes == 1, id_multiplicity == 1};
-  return from_hip(dgmi::spmm_sliced_bf16(a, as_stream(stream)));
+  return spmm_sliced(segptr, indices, vals, eid, keep, n_keep, X, 2, ldx, nullptr, dst_scale, Y, ldy, n_dst, n_src, F,
+                     n_slices, column_passes, id_multiplicity, planes, planes_bytes, act, act_slope, out_mask, ld_mask,
+                     out_mask_scale, stream);
 }
 
 DGMI_API int dgmi_gather_concat_f32(const int32_t* src, const int32_t* dst, int64_t E, const float* A,

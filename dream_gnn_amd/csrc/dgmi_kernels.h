@@ -1,6 +1,6 @@
 // dgmi_kernels.h — internal launch interface between the C ABI (dgmi_api.hip)
 // and the kernel translation units.  Not installed; the public contract is
-// include/dgmi.h.
+// include/dgmi*.h.  What only the two XCD-local SpMM units share is in dgmi_sliced_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -36,13 +36,14 @@ inline size_t plan_bytes(int64_t n_rows, int64_t nnz, int64_t chunk) {
 
 // Lanes-per-row for a 16-B-aligned width: the widest tile whose last tile is
 // still >= 85 % used (F=344 -> 32 lanes x 3 tiles, not 64 x 2 at 67 %).
-inline int pick_lpr(int64_t F) {
-  const int64_t f4 = (F + 3) / 4;
+// `cols`: columns per lane (one 16-B load: 4 fp32, 8 bf16); `widest`: the widest lane group the kernel is built for.
+inline int pick_lpr(int64_t F, int cols = 4, int widest = 64) {
+  const int64_t fc = (F + cols - 1) / cols;
   int best = 8;
   double best_util = 0.0;
-  for (int lpr : {64, 32, 16, 8}) {
-    const int64_t tiles = (f4 + lpr - 1) / lpr;
-    const double util = (double)f4 / (double)(tiles * lpr);
+  for (int lpr = widest; lpr >= 8; lpr /= 2) {
+    const int64_t tiles = (fc + lpr - 1) / lpr;
+    const double util = (double)fc / (double)(tiles * lpr);
     if (util >= 0.85) return lpr;
     if (util > best_util + 1e-9) {
       best_util = util;
@@ -114,7 +115,8 @@ hipError_t radix_sort_records(const int32_t* key, const int32_t* eid_in, const i
                               int32_t n_rows, int32_t n_cols, int32_t* keys_out, int32_t* eid_out, int32_t* col_out, int32_t* flag,
                               void* workspace, hipStream_t s);
 
-// Source-sliced CSR (dgmi_csr.hip) and the XCD-local SpMM over it (dgmi_sliced.hip).
+// Source-sliced CSR (dgmi_csr.hip) and the XCD-local SpMM over it (dgmi_sliced.hip, dgmi_sliced_bf16.hip; what the two
+// share: dgmi_sliced_common.h).
 hipError_t csr_sliced_from_coo_i32(const int32_t* row, const int32_t* col, int64_t E, int64_t n_rows,
                                    int64_t n_cols, int64_t n_slices, int64_t slice_width,
                                    int32_t* segptr, int32_t* indices, int32_t* eid, void* workspace,
@@ -136,9 +138,10 @@ struct SlicedArgs {
   const int32_t* segptr;   // n_slices * n_dst + 1
   const int32_t* indices;
   const float* vals;       // nullable, sliced order
-  const float* X;
-  int64_t ldx;
-  const float* src_scale;  // nullable
+  const void* X;           // the gathered table: fp32, or bf16 bit patterns
+  int x_bytes;             // bytes per element of X: 4 (spmm_sliced_f32) or 2 (spmm_sliced_bf16)
+  int64_t ldx;             // in elements; a multiple of 16 / x_bytes, as F is
+  const float* src_scale;  // nullable; must be null for a bf16 table (the scale belongs to rows_to_bf16)
   const float* dst_scale;  // nullable
   float* Y;
   int64_t ldy;
@@ -151,7 +154,7 @@ struct SlicedArgs {
   const void* keep;
   int n_keep;
   Epilogue ep;
-  bool full_width;         // never split the columns into half-width passes (see spmm_sliced_f32)
+  bool full_width;         // never split the columns into half-width passes (see sliced_lpr, dgmi_sliced_common.h)
   bool id_mult;            // vals == nullptr and the ids carry integer multiplicities (kMultShift)
 };
 
@@ -161,30 +164,9 @@ hipError_t row_multiplicity_f32(const int32_t* indptr, const float* vals, int64_
                                 int32_t* mult, int32_t* fail, hipStream_t s);
 hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s);
 
-// The same product gathering from a bf16 table (dgmi_sliced_bf16.hip): X holds bf16 bit patterns, ldx in elements
-// (a multiple of 8), F a multiple of 8; no source scale (it belongs to rows_to_bf16).  Planes, dst_scale, Y: fp32.
-struct SlicedBf16Args {
-  const int32_t* segptr;
-  const int32_t* indices;
-  const float* vals;       // nullable, sliced order
-  const uint16_t* X;
-  int64_t ldx;
-  const float* dst_scale;  // nullable
-  float* Y;
-  int64_t ldy;
-  int64_t n_dst, n_src, F;
-  int64_t n_slices;
-  float* planes;
-  int64_t ldp;
-  int64_t chunk_rows;
-  const int32_t* eid;
-  const void* keep;
-  int n_keep;
-  Epilogue ep;
-  bool full_width;
-  bool id_mult;
-};
-hipError_t spmm_sliced_bf16(const SlicedBf16Args& a, hipStream_t s);
+// The same product gathering from a bf16 table (dgmi_sliced_bf16.hip): x_bytes == 2, F and ldx multiples of 8, no source
+// scale (an error).  Planes, dst_scale, Y: fp32.
+hipError_t spmm_sliced_bf16(const SlicedArgs& a, hipStream_t s);
 // out[r, :] = bf16_rne(scale[r] * X[r, :]) (scale nullable), one streaming pass; F, ldo multiples of 8, ldx of 4
 hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t n, int64_t F, uint16_t* out, int64_t ldo,
                         hipStream_t s);

@@ -15,27 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dgmi_kernels.h"
-#include "dgmi_segment.h"
-#include "dgmi_tuning.h"
+#include "dgmi_sliced_common.h"
 
 namespace dgmi {
 namespace {
-
-constexpr int64_t kColumnPassMinRows = 32768;  // column passes only when a pass still has >= ~8k waves
-constexpr int kRowsPerGroup = 8;  // < LPR (row boundaries live one per lane of the group)
-constexpr int kTouchLead = 24;   // worker blocks of a slice between a toucher and the blocks it touches for
-constexpr int kTouchGroup = 8;   // worker blocks per toucher block
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
-  // one streaming 16-B store: the planes are write-once / read-once; keep them from evicting
-  // the XCD's slice of X out of L2
-  // (ordinary stores instead: the step of bench.py 3.03 ms against 2.85 ms, profiles/r03_swept_experiment/)
-  v4f t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
-}
 
 // A (row, slice) segment is short (deg / n_slices: 12-25 edges at config 4).  In the slice-major
 // layout the segments of consecutive rows of one slice are contiguous, so each LPR-lane *group*
@@ -86,43 +69,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel
   const int grp = lane / LPR, glane = lane % LPR, gbase = grp * LPR;
   const int slice = (int)(blockIdx.x % (unsigned)n_slices);
   int64_t block = blockIdx.x / (unsigned)n_slices;
-  if (touch_group > 0) {
-    // Touch-ahead.  The id stream and the row boundaries are read once, so a wave's first two loads (boundaries, then
-    // ids — dependent) miss every cache, and it gathers nothing for two memory latencies of its ~20 us life: inside a
-    // training step, where the other products have pushed this one's ids out of the Infinity Cache, that is 10-25 % of the
-    // product.  Every (touch_group + 1)-th block of a slice therefore gathers nothing: it touches the boundaries and the id
-    // lines (one word per 128-B line) of the touch_group worker blocks that start touch_lead worker blocks further on IN THE
-    // SAME SLICE — same XCD, same L2, a few microseconds later — and leaves.  Nobody waits for these loads but the toucher
-    // (vmcnt is in order: a worker that issued them would hold its own first gathers back).  A hint: results never depend on it.
-    const int64_t t = block / (touch_group + 1);
-    if (block % (touch_group + 1) == 0) {
-      __shared__ int range[2];
-      const int32_t* sp_s = segptr + (int64_t)slice * n_dst;
-      const int64_t rows_blk = (int64_t)kWavesPerBlock * G * R;
-      const int64_t r_first = row_begin + (t * touch_group + touch_lead) * rows_blk;
-      if (r_first >= row_end) return;  // block-uniform
-      const int64_t r_last = min(r_first + touch_group * rows_blk, row_end);
-      int keepalive = 0;
-      if (wave == 0) {  // lanes 0 / 1: the id range of those blocks; the others: one word per line of their boundaries
-        const int64_t rp = lane == 0 ? r_first : (lane == 1 ? r_last : r_first + (int64_t)(lane - 1) * 32);
-        if (rp <= r_last) {
-          const int v = sp_s[rp];
-          if (lane < 2) range[lane] = v;
-          keepalive = v;
-        }
-      }
-      __syncthreads();
-      const int e0 = range[0], e1 = range[1];
-      for (int64_t p = (int64_t)e0 + (int64_t)threadIdx.x * 32; p < e1; p += (int64_t)blockDim.x * 32) {
-        keepalive ^= indices[p];
-        if (HAS_VALS) keepalive ^= __float_as_int(vals[p]);
-        if (KEEP) keepalive ^= eid[p];
-      }
-      asm volatile("" ::"v"(keepalive));  // the loads exist, and are waited for, without an instruction
-      return;
-    }
-    block -= t + 1;  // worker blocks are numbered without the touchers
-  }
+  if (touch_group > 0 &&
+      touch_ahead<LPR, HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, R, touch_lead, touch_group,
+                                       lane, wave, block))
+    return;
   const int64_t row0 = row_begin + ((block * kWavesPerBlock + wave) * G + grp) * R;
   if (row0 >= row_end) return;  // whole group idle (lanes of other groups carry on)
   const int nr = (int)(row0 + R <= row_end ? R : row_end - row0);
@@ -300,43 +250,37 @@ __global__ __launch_bounds__(256) void reduce_planes_kernel(const float* __restr
   }
 }
 
+// The reduce of one row chunk: planes, dst_scale, Y and ep.mask all start at the chunk's first row.
+hipError_t reduce_planes(const float* planes, int64_t ldp, int64_t rows, int64_t F, int64_t n_slices, const float* ds, float* y,
+                         int64_t ldy, const Epilogue& ep, hipStream_t s) {
+  const int F4 = (int)(F / 4);
+  int64_t blocks = (rows * F4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+#define DGMI_REDUCE(D, S)                                                                                        \
+  hipLaunchKernelGGL((reduce_planes_kernel<D, S>), dim3((unsigned)blocks), dim3(256), 0, s, planes, ldp, rows, F4, \
+                     (int)n_slices, ds, y, ldy, ep)
+  if (n_slices == 8) {
+    if (ds) DGMI_REDUCE(true, 8); else DGMI_REDUCE(false, 8);
+  } else {
+    if (ds) DGMI_REDUCE(true, 0); else DGMI_REDUCE(false, 0);
+  }
+#undef DGMI_REDUCE
+  return hipGetLastError();
+}
+
 template <int LPR>
 hipError_t launch_sliced(const SlicedArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
-  constexpr int G = kWave / LPR;
-  // Rows per lane group.  In the step (cold id stream, touch-ahead on), G edges/s at 4 / 6 / 8 / 12 / 15 rows: half-width
-  // products 31.8 / 31.2 / 30.8 / 28.2 / 27.9, full-width ones 28.4 / 29.5 / 30.1 / 30.2 / 30.3, the step 30.8 / 31.0 / 31.0 /
-  // 30.1 / 29.7.  One value for every width: where a group's run starts decides how its batches of 8 are cut, so a
-  // width-dependent value would make the column passes round differently from the full-width pass (they are bit-identical,
-  // test_xcd_sliced_column_passes).  Tuning::sliced_rows forces a value (tools).
-  const Tuning& tune = tuning();
-  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : kRowsPerGroup;
-  const int R = rows_req < 1 ? 1 : (rows_req < LPR ? rows_req : LPR - 1);
-  const int64_t per_block = (int64_t)kWavesPerBlock * G * R;
-  const int64_t blocks = (row_end - row_begin + per_block - 1) / per_block;
+  const SlicedGeometry g = sliced_geometry(row_begin, row_end, a.F, a.n_src, a.ldx, a.n_slices, LPR, a.x_bytes);
   dim3 block(kWave * kWavesPerBlock);
   const int key = (a.vals ? 4 : (a.id_mult ? 8 : 0)) | (a.src_scale ? 2 : 0) | (a.n_keep > 0 ? 1 : 0);
-  const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * 4 < ((int64_t)1 << 32);
-  // Touch-ahead (see the kernel): one toucher per kTouchGroup worker blocks, kTouchLead worker blocks ahead.  An XCD starts
-  // ~7 blocks of its slice per us, so 24 blocks are ~3.5 us of lead — a memory latency, and short enough for the touched
-  // lines to still be in its L2.  Step of bench.py: no touching 2.724 ms; wave 0 of every block touching for the block 16 /
-  // 24 / 32 further on 2.553 / 2.548 / 2.548; toucher blocks, one per 4 / 8 / 16 workers 2.526 / 2.528 / 2.530
-  // (profiles/r03_touch_ahead/).  Tuning::sliced_touch_lead overrides the lead (tools/cold_ids_probe.py; 0 = no touchers).
-  const int touch_lead = tune.sliced_touch_lead >= 0 ? tune.sliced_touch_lead : kTouchLead;
-  const int touch_group = touch_lead > 0 ? kTouchGroup : 0;
-  const int64_t touchers = touch_group > 0 ? (blocks + touch_group - 1) / touch_group : 0;
-  dim3 grid((unsigned)((blocks + touchers) * a.n_slices), (unsigned)((a.F + 4 * LPR - 1) / (4 * LPR)));
-#define DGMI_LAUNCH(V, S, K)                                                                                    \
-  do {                                                                                                          \
-    if (off32)                                                                                                  \
-      hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, V, S, K, true>), grid, block, 0, s, a.segptr, a.indices,  \
-                         a.vals, a.X, a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end,          \
-                         (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep,       \
-                         touch_lead, R, touch_group);                                                             \
-    else                                                                                                        \
-      hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, V, S, K, false>), grid, block, 0, s, a.segptr, a.indices, \
-                         a.vals, a.X, a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end,          \
-                         (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep,       \
-                         touch_lead, R, touch_group);                                                             \
+#define DGMI_LAUNCH_O(V, S, K, O)                                                                                      \
+  hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, V, S, K, O>), g.grid, block, 0, s, a.segptr, a.indices, a.vals,      \
+                     static_cast<const float*>(a.X), a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end, \
+                     (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.R, \
+                     g.touch_group)
+#define DGMI_LAUNCH(V, S, K)                                              \
+  do {                                                                    \
+    if (g.off32) DGMI_LAUNCH_O(V, S, K, true); else DGMI_LAUNCH_O(V, S, K, false); \
   } while (0)
   switch (key) {
     case 0: DGMI_LAUNCH(0, false, false); break;
@@ -353,71 +297,44 @@ hipError_t launch_sliced(const SlicedArgs& a, int64_t row_begin, int64_t row_end
     default: DGMI_LAUNCH(2, true, true); break;
   }
 #undef DGMI_LAUNCH
+#undef DGMI_LAUNCH_O
   return hipGetLastError();
+}
+
+hipError_t launch_gather_f32(const SlicedArgs& a, int lpr, int64_t r0, int64_t r1, hipStream_t s) {
+  switch (lpr) {
+    case 8: return launch_sliced<8>(a, r0, r1, s);
+    case 16: return launch_sliced<16>(a, r0, r1, s);
+    case 32: return launch_sliced<32>(a, r0, r1, s);
+    default: return launch_sliced<64>(a, r0, r1, s);
+  }
 }
 
 }  // namespace
 
-hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s) {
+hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStream_t s) {
   if (a.n_dst == 0 || a.F == 0) return hipSuccess;
-  const int F4 = (int)(a.F / 4);
   // Row chunks: the 8 partial planes of a chunk (chunk_rows * n_slices * 4F bytes, <= ~32 MB) are
   // written and read back while still resident in the 256 MiB Infinity Cache, and the same
   // plane buffer is reused by every chunk.
   const int64_t chunk = a.chunk_rows > 0 ? a.chunk_rows : a.n_dst;
   for (int64_t r0 = 0; r0 < a.n_dst; r0 += chunk) {
     const int64_t r1 = r0 + chunk < a.n_dst ? r0 + chunk : a.n_dst;
-    hipError_t err;
-    // Lane-group width = column tile.  Widest group whose last column tile is still >= 85 % used — unless
-    // the slice of X one XCD gathers from (n_src / n_slices rows x 16 LPR bytes) is larger than its 4 MiB
-    // L2: then half the width.  The column tiles are grid.y, dispatched one after the other, so the XCD
-    // sweeps its slice twice at half the footprint.  Measured at F = 128: 100k-source table (6.4 -> 3.2 MB
-    // per pass, bench.py) 0.379 -> 0.365 ms unweighted, 0.512 -> 0.464 ms kNN-64 weighted; config-5 shards
-    // (tools/cfg5_forms_probe.py) 204 MB table 0.740 -> 0.663 ms, 409 MB table 0.741 -> 0.712 ms (the halves
-    // of all 8 slices together fit the 256 MiB Infinity Cache; a quarter width gains nothing more).  A
-    // 50k-source table (already 3.2 MB per slice) loses 10-18 % when halved, so the rule is tied to the
-    // footprint; and a graph whose time is set by a few very long (virtual) rows pays their dependent gather
-    // chain once per pass (Zipf(1.2) cut into 2048-edge virtual rows: 0.47 -> 0.62 ms; at the 512 edges
-    // ops._SplitSliced uses the passes win again, 0.435 -> 0.418 ms): such a caller can ask for full width.
-    // With edge dropout on the fly every pass re-evaluates keep(eid[p]) per edge (0.386 -> 0.408 ms): full width.
-    // Half-width groups also mean half as many waves per pass (n_dst / 4 at F = 128): with few, long rows the
-    // launch no longer fills the chip (config-5 edge-scaled shard, 6250 rows of 1600 edges: 0.382 -> 0.440 ms),
-    // so the rule needs kColumnPassMinRows destination rows.
-    // Tuning::sliced_lpr forces a width (tools).
-    const int forced_lpr = tuning().sliced_lpr;
-    int lpr = pick_lpr(a.F);
-    if (lpr >= 32 && !a.full_width && a.n_keep == 0 && a.n_dst >= kColumnPassMinRows) {
-      const int64_t width = 16 * (int64_t)lpr < 4 * a.F ? 16 * (int64_t)lpr : 4 * a.F;
-      const int64_t slice_bytes = (a.n_src + a.n_slices - 1) / a.n_slices * width;
-      if (slice_bytes > (4 << 20)) lpr /= 2;
-    }
-    if (forced_lpr == 8 || forced_lpr == 16 || forced_lpr == 32 || forced_lpr == 64) lpr = forced_lpr;
-    switch (lpr) {
-      case 8: err = launch_sliced<8>(a, r0, r1, s); break;
-      case 16: err = launch_sliced<16>(a, r0, r1, s); break;
-      case 32: err = launch_sliced<32>(a, r0, r1, s); break;
-      default: err = launch_sliced<64>(a, r0, r1, s); break;
-    }
+    const int lpr = sliced_lpr(a.F, a.n_src, a.n_slices, a.n_dst, a.full_width, a.n_keep, a.x_bytes, tuning().sliced_lpr);
+    hipError_t err = gather(a, lpr, r0, r1, s);
     if (err != hipSuccess) return err;
-    int64_t blocks = ((r1 - r0) * F4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    const float* ds = a.dst_scale ? a.dst_scale + r0 : nullptr;
-    float* y = a.Y + r0 * a.ldy;
     Epilogue ep = a.ep;  // rows of this chunk start at r0
     if (ep.mask != nullptr) ep.mask += r0 * ep.ldm;
-#define DGMI_REDUCE(D, S)                                                                               \
-  hipLaunchKernelGGL((reduce_planes_kernel<D, S>), dim3((unsigned)blocks), dim3(256), 0, s, a.planes, a.ldp, \
-                     r1 - r0, F4, (int)a.n_slices, ds, y, a.ldy, ep)
-    if (a.n_slices == 8) {
-      if (ds) DGMI_REDUCE(true, 8); else DGMI_REDUCE(false, 8);
-    } else {
-      if (ds) DGMI_REDUCE(true, 0); else DGMI_REDUCE(false, 0);
-    }
-#undef DGMI_REDUCE
-    err = hipGetLastError();
+    err = reduce_planes(a.planes, a.ldp, r1 - r0, a.F, a.n_slices, a.dst_scale ? a.dst_scale + r0 : nullptr, a.Y + r0 * a.ldy,
+                        a.ldy, ep, s);
     if (err != hipSuccess) return err;
   }
   return hipSuccess;
+}
+
+hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s) {
+  if (a.x_bytes != 4) return hipErrorInvalidValue;
+  return spmm_sliced_chunks(a, launch_gather_f32, s);
 }
 
 }  // namespace dgmi

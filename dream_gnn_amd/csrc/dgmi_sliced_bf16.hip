@@ -16,28 +16,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dgmi_kernels.h"
-#include "dgmi_segment.h"
-#include "dgmi_tuning.h"
+#include "dgmi_sliced_common.h"
 
 namespace dgmi {
 namespace {
 
-constexpr int64_t kColumnPassMinRows = 32768;  // as dgmi_sliced.hip
-constexpr int kRowsPerGroup = 8;
-constexpr int kTouchLead = 24;
-constexpr int kTouchGroup = 8;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
-  // one streaming 16-B store (dgmi_sliced.hip): the planes are write-once / read-once
-  v4f t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
-}
 
 // two fp32 -> one dword of two bf16, round-to-nearest-even (v_cvt_pk_bf16_f32); element 0 in the low half
 __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
@@ -109,8 +95,8 @@ __device__ __forceinline__ void batch_pair(const v4u (&raw)[kUnroll], const floa
   acc1 += (hi[0] + hi[1]) + (hi[2] + hi[3]);
 }
 
-// The gather of spmm_sliced_vec4_kernel (dgmi_sliced.hip) with 8 columns per lane: see there for the grid, the
-// touch-ahead blocks, KEEP and VALS.  Every float4 operation of that kernel is done twice here (columns 0..3 in `a`,
+// The gather of spmm_sliced_vec4_kernel (dgmi_sliced.hip) with 8 columns per lane: see there for the grid, KEEP and
+// VALS, and touch_ahead (dgmi_sliced_common.h) for the toucher blocks.  Every float4 operation of that kernel is done twice here (columns 0..3 in `a`,
 // 4..7 in `b`), in the same order.  Built for five waves per SIMD (96 VGPRs) like that kernel's forms without a source scale;
 // a per-edge weight together with dropout on the fly or with 8-lane groups needs 100-109 VGPRs: four waves, no scratch.
 template <int LPR, int VALS, bool KEEP, bool OFF32>
@@ -130,38 +116,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR =
   const int grp = lane / LPR, glane = lane % LPR, gbase = grp * LPR;
   const int slice = (int)(blockIdx.x % (unsigned)n_slices);
   int64_t block = blockIdx.x / (unsigned)n_slices;
-  if (touch_group > 0) {
-    // touch-ahead: every (touch_group + 1)-th block of a slice gathers nothing and touches the boundaries and id lines
-    // of the worker blocks touch_lead further on in the same slice (dgmi_sliced.hip); a hint, results never depend on it
-    const int64_t t = block / (touch_group + 1);
-    if (block % (touch_group + 1) == 0) {
-      __shared__ int range[2];
-      const int32_t* sp_s = segptr + (int64_t)slice * n_dst;
-      const int64_t rows_blk = (int64_t)kWavesPerBlock * G * R;
-      const int64_t r_first = row_begin + (t * touch_group + touch_lead) * rows_blk;
-      if (r_first >= row_end) return;  // block-uniform
-      const int64_t r_last = min(r_first + touch_group * rows_blk, row_end);
-      int keepalive = 0;
-      if (wave == 0) {
-        const int64_t rp = lane == 0 ? r_first : (lane == 1 ? r_last : r_first + (int64_t)(lane - 1) * 32);
-        if (rp <= r_last) {
-          const int v = sp_s[rp];
-          if (lane < 2) range[lane] = v;
-          keepalive = v;
-        }
-      }
-      __syncthreads();
-      const int e0 = range[0], e1 = range[1];
-      for (int64_t p = (int64_t)e0 + (int64_t)threadIdx.x * 32; p < e1; p += (int64_t)blockDim.x * 32) {
-        keepalive ^= indices[p];
-        if (HAS_VALS) keepalive ^= __float_as_int(vals[p]);
-        if (KEEP) keepalive ^= eid[p];
-      }
-      asm volatile("" ::"v"(keepalive));
-      return;
-    }
-    block -= t + 1;  // worker blocks are numbered without the touchers
-  }
+  if (touch_group > 0 &&
+      touch_ahead<LPR, HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, R, touch_lead, touch_group,
+                                       lane, wave, block))
+    return;
   const int64_t row0 = row_begin + ((block * kWavesPerBlock + wave) * G + grp) * R;
   if (row0 >= row_end) return;  // whole group idle
   const int nr = (int)(row0 + R <= row_end ? R : row_end - row0);
@@ -275,109 +233,19 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR =
   }
 }
 
-// The plane reduce of dgmi_sliced.hip, restated here so that that file's instantiations stay what they are:
-// Y[row] = dst_scale[row] * (plane_0[row] + plane_1[row] + ...) in slice order; planes, dst_scale, Epilogue and Y are fp32.
-template <bool HAS_DS, int S>
-__global__ __launch_bounds__(256) void reduce_planes_kernel(const float* __restrict__ planes, int64_t ldp,
-                                                            int64_t rows, int F4, int n_slices,
-                                                            const float* __restrict__ dst_scale,
-                                                            float* __restrict__ Y, int64_t ldy, Epilogue ep) {
-  const int64_t total = rows * F4;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const int64_t plane_stride = rows * ldp;
-  const bool dense = (ldp == 4 * (int64_t)F4) && (ldy == ldp);  // element t of a plane is at offset 4t
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
-    int64_t row, poff, yoff;
-    if (dense) {
-      row = t / F4;
-      poff = yoff = 4 * t;
-    } else {
-      row = t / F4;
-      const int c = (int)(t - row * F4) * 4;
-      poff = row * ldp + c;
-      yoff = row * ldy + c;
-    }
-    const float* p = planes + poff;
-    float4 acc;
-    if (S > 0) {
-      float4 v[S > 0 ? S : 1];
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p + s * plane_stride));
-        v[s] = make_float4(t.x, t.y, t.z, t.w);
-      }
-      acc = v[0];
-#pragma unroll
-      for (int s = 1; s < S; ++s) {
-        acc.x += v[s].x;
-        acc.y += v[s].y;
-        acc.z += v[s].z;
-        acc.w += v[s].w;
-      }
-    } else {
-      acc = *reinterpret_cast<const float4*>(p);
-      for (int s = 1; s < n_slices; ++s) {
-        const float4 v = *reinterpret_cast<const float4*>(p + s * plane_stride);
-        acc.x += v.x;
-        acc.y += v.y;
-        acc.z += v.z;
-        acc.w += v.w;
-      }
-    }
-    if (HAS_DS) {
-      const float d = dst_scale[row];
-      acc.x *= d;
-      acc.y *= d;
-      acc.z *= d;
-      acc.w *= d;
-    }
-    *reinterpret_cast<float4*>(Y + yoff) = epilogue4(ep, acc, row, (int)(yoff - row * ldy));
-  }
-}
-
-// pick_lpr (dgmi_kernels.h) on F / 8 lanes, widths 32 / 16 / 8: the widest tile whose last tile is >= 85 % used
-int pick_lpr_bf16(int64_t F) {
-  const int64_t f8 = (F + 7) / 8;
-  int best = 8;
-  double best_util = 0.0;
-  for (int lpr : {32, 16, 8}) {
-    const int64_t tiles = (f8 + lpr - 1) / lpr;
-    const double util = (double)f8 / (double)(tiles * lpr);
-    if (util >= 0.85) return lpr;
-    if (util > best_util + 1e-9) {
-      best_util = util;
-      best = lpr;
-    }
-  }
-  return best;
-}
-
 template <int LPR>
-hipError_t launch_sliced_bf16(const SlicedBf16Args& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
-  constexpr int G = kWave / LPR;
-  // rows per lane group, touch-ahead, 32-bit offsets: the rules and the Tuning knobs of launch_sliced (dgmi_sliced.hip)
-  const Tuning& tune = tuning();
-  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : kRowsPerGroup;
-  const int R = rows_req < 1 ? 1 : (rows_req < LPR ? rows_req : LPR - 1);
-  const int64_t per_block = (int64_t)kWavesPerBlock * G * R;
-  const int64_t blocks = (row_end - row_begin + per_block - 1) / per_block;
+hipError_t launch_sliced_bf16(const SlicedArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
+  const SlicedGeometry g = sliced_geometry(row_begin, row_end, a.F, a.n_src, a.ldx, a.n_slices, LPR, a.x_bytes);
   dim3 block(kWave * kWavesPerBlock);
   const int key = (a.vals ? 2 : (a.id_mult ? 4 : 0)) | (a.n_keep > 0 ? 1 : 0);
-  const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * 2 < ((int64_t)1 << 32);
-  const int touch_lead = tune.sliced_touch_lead >= 0 ? tune.sliced_touch_lead : kTouchLead;
-  const int touch_group = touch_lead > 0 ? kTouchGroup : 0;
-  const int64_t touchers = touch_group > 0 ? (blocks + touch_group - 1) / touch_group : 0;
-  dim3 grid((unsigned)((blocks + touchers) * a.n_slices), (unsigned)((a.F + 8 * LPR - 1) / (8 * LPR)));
-#define DGMI_LAUNCH(V, K)                                                                                          \
-  do {                                                                                                             \
-    if (off32)                                                                                                     \
-      hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, true>), grid, block, 0, s, a.segptr, a.indices, a.vals, \
-                         a.X, a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices, a.eid, \
-                         static_cast<const KeepSeg*>(a.keep), a.n_keep, touch_lead, R, touch_group);                \
-    else                                                                                                           \
-      hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, false>), grid, block, 0, s, a.segptr, a.indices, a.vals, \
-                         a.X, a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices, a.eid, \
-                         static_cast<const KeepSeg*>(a.keep), a.n_keep, touch_lead, R, touch_group);                \
+#define DGMI_LAUNCH_O(V, K, O)                                                                                         \
+  hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, O>), g.grid, block, 0, s, a.segptr, a.indices, a.vals,        \
+                     static_cast<const uint16_t*>(a.X), a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, \
+                     (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.R,         \
+                     g.touch_group)
+#define DGMI_LAUNCH(V, K)                                                    \
+  do {                                                                       \
+    if (g.off32) DGMI_LAUNCH_O(V, K, true); else DGMI_LAUNCH_O(V, K, false); \
   } while (0)
   switch (key) {
     case 0: DGMI_LAUNCH(0, false); break;
@@ -388,7 +256,16 @@ hipError_t launch_sliced_bf16(const SlicedBf16Args& a, int64_t row_begin, int64_
     default: DGMI_LAUNCH(2, true); break;
   }
 #undef DGMI_LAUNCH
+#undef DGMI_LAUNCH_O
   return hipGetLastError();
+}
+
+hipError_t launch_gather_bf16(const SlicedArgs& a, int lpr, int64_t r0, int64_t r1, hipStream_t s) {
+  switch (lpr) {
+    case 8: return launch_sliced_bf16<8>(a, r0, r1, s);
+    case 16: return launch_sliced_bf16<16>(a, r0, r1, s);
+    default: return launch_sliced_bf16<32>(a, r0, r1, s);
+  }
 }
 
 }  // namespace
@@ -406,49 +283,11 @@ hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t
   return hipGetLastError();
 }
 
-hipError_t spmm_sliced_bf16(const SlicedBf16Args& a, hipStream_t s) {
-  if (a.n_dst == 0 || a.F == 0) return hipSuccess;
-  const int F4 = (int)(a.F / 4);
-  const int64_t chunk = a.chunk_rows > 0 ? a.chunk_rows : a.n_dst;  // row chunks as spmm_sliced_f32
-  for (int64_t r0 = 0; r0 < a.n_dst; r0 += chunk) {
-    const int64_t r1 = r0 + chunk < a.n_dst ? r0 + chunk : a.n_dst;
-    hipError_t err;
-    // Lane-group width = column tile of 8 * LPR columns.  The column-pass rule of spmm_sliced_f32 on the bytes of a bf16
-    // slice: half the width when the slice one XCD gathers from (n_src / n_slices rows x 16 LPR bytes) exceeds its 4 MiB
-    // L2 — at 2 bytes per column a 100 000-source table at F = 128 (3.2 MB per slice) stays at full width.
-    const int forced_lpr = tuning().sliced_lpr;
-    int lpr = pick_lpr_bf16(a.F);
-    if (lpr >= 32 && !a.full_width && a.n_keep == 0 && a.n_dst >= kColumnPassMinRows) {
-      const int64_t width = 16 * (int64_t)lpr < 2 * a.F ? 16 * (int64_t)lpr : 2 * a.F;
-      const int64_t slice_bytes = (a.n_src + a.n_slices - 1) / a.n_slices * width;
-      if (slice_bytes > (4 << 20)) lpr /= 2;
-    }
-    if (forced_lpr == 8 || forced_lpr == 16 || forced_lpr == 32) lpr = forced_lpr;
-    switch (lpr) {
-      case 8: err = launch_sliced_bf16<8>(a, r0, r1, s); break;
-      case 16: err = launch_sliced_bf16<16>(a, r0, r1, s); break;
-      default: err = launch_sliced_bf16<32>(a, r0, r1, s); break;
-    }
-    if (err != hipSuccess) return err;
-    int64_t blocks = ((r1 - r0) * F4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    const float* ds = a.dst_scale ? a.dst_scale + r0 : nullptr;
-    float* y = a.Y + r0 * a.ldy;
-    Epilogue ep = a.ep;  // rows of this chunk start at r0
-    if (ep.mask != nullptr) ep.mask += r0 * ep.ldm;
-#define DGMI_REDUCE(D, S)                                                                               \
-  hipLaunchKernelGGL((reduce_planes_kernel<D, S>), dim3((unsigned)blocks), dim3(256), 0, s, a.planes, a.ldp, \
-                     r1 - r0, F4, (int)a.n_slices, ds, y, a.ldy, ep)
-    if (a.n_slices == 8) {
-      if (ds) DGMI_REDUCE(true, 8); else DGMI_REDUCE(false, 8);
-    } else {
-      if (ds) DGMI_REDUCE(true, 0); else DGMI_REDUCE(false, 0);
-    }
-#undef DGMI_REDUCE
-    err = hipGetLastError();
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+// Row chunks and the plane reduce: spmm_sliced_chunks (dgmi_sliced.hip); the column-pass rule, here on the bytes of a
+// bf16 slice: sliced_lpr (dgmi_sliced_common.h).
+hipError_t spmm_sliced_bf16(const SlicedArgs& a, hipStream_t s) {
+  if (a.x_bytes != 2 || a.src_scale != nullptr) return hipErrorInvalidValue;  // the source scale belongs to rows_to_bf16
+  return spmm_sliced_chunks(a, launch_gather_bf16, s);
 }
 
 }  // namespace dgmi

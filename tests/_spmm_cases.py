@@ -163,7 +163,8 @@ def reference_int64(dst, src, n_dst, X, w=None, ss=None, kept=None):
 
 
 # ---------------------------------------------------------------------------------------------
-# launch geometry: csrc/dgmi_sliced.hip (launch_sliced / spmm_sliced_f32), csrc/dgmi_kernels.h (pick_lpr)
+# launch geometry: csrc/dgmi_sliced_common.h (sliced_geometry; the chunks: spmm_sliced_chunks in csrc/dgmi_sliced.hip),
+# csrc/dgmi_kernels.h (pick_lpr)
 # ---------------------------------------------------------------------------------------------
 WAVE, WAVES_PER_BLOCK, ROWS_PER_GROUP, TOUCH_LEAD, TOUCH_GROUP = 64, 4, 8, 24, 8
 

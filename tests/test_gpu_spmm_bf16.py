@@ -54,7 +54,7 @@ def _stage(dev, n_slices):
 
 
 def pick_lpr_bf16(F):
-    """``pick_lpr`` of the fp32 kernel on F / 8 lanes, widths 32 / 16 / 8 (csrc/dgmi_sliced_bf16.hip)."""
+    """``pick_lpr(F, 8, 32)`` (csrc/dgmi_kernels.h): ``pick_lpr`` of the fp32 kernel on F / 8 lanes, widths 32 / 16 / 8."""
     f8 = (F + 7) // 8
     best, best_util = 8, 0.0
     for lpr in (32, 16, 8):
@@ -284,6 +284,47 @@ def test_bit_identical_to_the_fp32_kernel_on_the_upcast_table(dev, kind, F):
                 assert torch.equal(a, b), (rows, chunk, keep is not None, int((a != b).sum()))
                 assert torch.equal(a, sl.spmm(Xb, None, st["ds"], keep=keep, **kw))  # reproducible
         assert float(a.abs().max()) > 1.0
+    finally:
+        for name, value in C.DEFAULTS.items():
+            _lib.set_tuning(name, value)
+
+
+def column_pass_lpr(F, n_src, n_slices, n_dst, elem_bytes):
+    """``sliced_lpr`` (csrc/dgmi_sliced_common.h) for a plain product (no ``full_width``, no dropout on the fly, no forced
+    width): half the width when the slice one XCD gathers from exceeds its 4 MiB L2."""
+    lpr = C.pick_lpr(F) if elem_bytes == 4 else pick_lpr_bf16(F)
+    if lpr >= 32 and n_dst >= 32768 and -(-n_src // n_slices) * min(16 * lpr, elem_bytes * F) > 4 << 20:
+        lpr //= 2
+    return lpr
+
+
+def test_column_passes_on_bf16_bytes(dev):
+    """Bit-identity ACROSS the column-pass threshold on bf16 bytes.  32 768 rows (the rule's floor), F = 256, 8 slices:
+    at 65 537 sources a bf16 slice is 8 193 rows x 512 B, one row over 4 MiB, where the rule asks for two half-width
+    passes; at 65 536 it does not (the fp32 product halves at both).  Random normal bf16 tables, so every sum rounds: the
+    product equals, bitwise, its own single full-width pass and the fp32 kernel's full-width pass over the upcast table —
+    also with 16-lane groups forced.  Half and full width are bit-identical by design, so this does NOT observe which
+    width the library launched: the threshold itself is asserted on the host restatement ``column_pass_lpr`` only."""
+    from dream_gnn_amd import _lib, ops
+
+    n_dst, F, n_slices = 32768, 256, 8
+    assert [column_pass_lpr(F, n, n_slices, n_dst, 2) for n in (65537, 65536)] == [16, 32]
+    assert [column_pass_lpr(F, n, n_slices, n_dst, 4) for n in (65537, 65536)] == [32, 32] and C.pick_lpr(F) == 64
+    assert column_pass_lpr(F, 65537, n_slices, n_dst - 1, 2) == 32
+    rng = np.random.default_rng(256)
+    try:
+        for n_src in (65537, 65536):
+            dst = np.repeat(np.arange(n_dst), rng.integers(0, 9, n_dst)).astype(np.int32)  # about 4 edges per row
+            src = rng.integers(0, n_src, dst.size).astype(np.int32)
+            sl = ops.SlicedCSR(_t(dst, dev), _t(src, dev), n_dst, n_src, n_slices=n_slices)
+            g = torch.Generator(device="cpu").manual_seed(n_src)
+            Xb = torch.randn(n_src, F, generator=g).to(dev).to(BF16)
+            for lpr in (0, 16):
+                _lib.set_tuning("sliced_lpr", lpr)
+                y = sl.spmm(Xb)
+                assert torch.equal(y, sl.spmm(Xb, full_width=True)), (n_src, lpr)
+                assert torch.equal(y, sl.spmm(Xb.float(), full_width=True)), (n_src, lpr)
+            assert float(y.abs().max()) > 1.0
     finally:
         for name, value in C.DEFAULTS.items():
             _lib.set_tuning(name, value)
