@@ -26,10 +26,17 @@ namespace {
 // run — ids read LPR at a time by the group's own lanes, one gathered source row per group per
 // wave-instruction, 8 gathers in flight per group — and cuts the running sum at the row
 // boundaries (held one per lane, fetched with ds_bpermute when crossed).  No bubble between
-// rows, no cross-group reduction.  Within a row the sum is sequential in edge order.
+// rows, no cross-group reduction.
 //
-// grid.x = n_slices * (worker blocks + toucher blocks), worker blocks = ceil(rows / (4 waves * G groups * kRowsPerGroup));
-// block b: slice = b % n_slices.
+// The sum of a (row, slice) segment is CANONICAL: acc starts at +0 and takes the segment's edges in layout order,
+// acc = acc + x_p (unit values) or acc = fmaf(w_p, x_p, acc) (w_p: the edge's factors multiplied in the order below),
+// whether a batch of 8 lies inside one row (no boundary tests) or crosses a boundary (per-edge tests).  With the planes
+// added in slice order, a product is a function of the layout and the operands alone: not of the rows per lane group,
+// the lane-group width, the row chunks, the column passes, the tapered tail, the touchers or — for a table of bf16 values
+// — of the table's element width (dgmi_sliced_bf16.hip computes the same).
+//
+// grid.x = n_slices * (worker blocks + toucher blocks); the rows of a worker block's lane groups: sliced_run
+// (dgmi_sliced_common.h).  block b: slice = b % n_slices.
 // Rows [row_begin, row_end) of every slice; plane row index is relative to row_begin.
 // KEEP: edge dropout on the fly — an edge whose keep(eid[p]) fails (dgmi_keep.h) is flagged in the sign
 // bit of its source id; its gather repeats the group's previous row (an L1 hit — never one fixed row,
@@ -56,9 +63,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel
     const float* __restrict__ vals, const float* __restrict__ X, int64_t ldx,
     const float* __restrict__ src_scale, float* __restrict__ planes, int64_t ldp, int64_t n_dst,
     int64_t row_begin, int64_t row_end, int F, int n_slices, const int32_t* __restrict__ eid,
-    const KeepSeg* __restrict__ keep, int n_keep, int touch_lead, int rows_per_group, int touch_group) {
+    const KeepSeg* __restrict__ keep, int n_keep, int touch_lead, SlicedRuns runs, int touch_group) {
   constexpr int G = kWave / LPR;
-  const int R = rows_per_group;  // < LPR: a group's row boundaries live one per lane
   constexpr bool HAS_VALS = VALS == 1;
   constexpr bool MULT = VALS == 2;
   constexpr bool WEIGHTED = HAS_VALS || HAS_SS || MULT;  // a per-edge factor exists
@@ -70,12 +76,13 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel
   const int slice = (int)(blockIdx.x % (unsigned)n_slices);
   int64_t block = blockIdx.x / (unsigned)n_slices;
   if (touch_group > 0 &&
-      touch_ahead<LPR, HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, R, touch_lead, touch_group,
-                                       lane, wave, block))
+      touch_ahead<HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, runs, touch_lead, touch_group,
+                                  lane, wave, block))
     return;
-  const int64_t row0 = row_begin + ((block * kWavesPerBlock + wave) * G + grp) * R;
-  if (row0 >= row_end) return;  // whole group idle (lanes of other groups carry on)
-  const int nr = (int)(row0 + R <= row_end ? R : row_end - row0);
+  const SlicedRun run = sliced_run(runs, block, wave * G + grp);
+  const int nr = run.rows;  // < LPR: a group's row boundaries live one per lane
+  if (nr == 0) return;  // whole group idle (lanes of other groups carry on)
+  const int64_t row0 = row_begin + run.first;
   int col = ((int)blockIdx.y * LPR + glane) * 4;
   const bool col_ok = col < F;
   if (!col_ok) col = 0;
@@ -138,24 +145,25 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel
         v[u] = ld_row<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
         if (dropped) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
-      // fast path (group-uniform): all 8 edges belong to the current row -> balanced tree, no
-      // per-edge boundary tests (a timing-only build that took it for EVERY batch gained 2-7 %: the slow path is not
-      // what holds the kernel at 0.81 of the gather probe — profiles/r03_swept_experiment/README.md)
+      // fast path (group-uniform): all 8 edges belong to the current row -> no per-edge boundary tests; the same
+      // in-order sum as below (the four columns are the ILP) (a timing-only build that took it for EVERY batch gained
+      // 2-7 %: the slow path is not what holds the kernel at 0.81 of the gather probe —
+      // profiles/r03_swept_experiment/README.md)
       if (base + j + kUnroll <= next_b) {
-        if (WEIGHTED) {
 #pragma unroll
-          for (int u = 0; u < kUnroll; ++u) {
-            v[u].x *= w[u];
-            v[u].y *= w[u];
-            v[u].z *= w[u];
-            v[u].w *= w[u];
+        for (int u = 0; u < kUnroll; ++u) {
+          if (WEIGHTED) {
+            acc.x = fmaf(w[u], v[u].x, acc.x);
+            acc.y = fmaf(w[u], v[u].y, acc.y);
+            acc.z = fmaf(w[u], v[u].z, acc.z);
+            acc.w = fmaf(w[u], v[u].w, acc.w);
+          } else {
+            acc.x += v[u].x;
+            acc.y += v[u].y;
+            acc.z += v[u].z;
+            acc.w += v[u].w;
           }
         }
-        tree_sum(v, kUnroll);
-        acc.x += v[0].x;
-        acc.y += v[0].y;
-        acc.z += v[0].z;
-        acc.w += v[0].w;
         continue;
       }
 #pragma unroll
@@ -276,7 +284,7 @@ hipError_t launch_sliced(const SlicedArgs& a, int64_t row_begin, int64_t row_end
 #define DGMI_LAUNCH_O(V, S, K, O)                                                                                      \
   hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, V, S, K, O>), g.grid, block, 0, s, a.segptr, a.indices, a.vals,      \
                      static_cast<const float*>(a.X), a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end, \
-                     (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.R, \
+                     (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.runs, \
                      g.touch_group)
 #define DGMI_LAUNCH(V, S, K)                                              \
   do {                                                                    \

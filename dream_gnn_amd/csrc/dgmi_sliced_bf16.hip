@@ -9,9 +9,8 @@
 //   Y[i]   = dst_scale[i] * sum_{e: dst(e) = i} w_e * float(xb[src(e)])          (products, sums, planes, Y: fp32)
 //
 // Layout (segptr, id words, multiplicity bits 28..30, dropped flag in bit 31), row-boundary logic, touch-ahead blocks,
-// batches of 8 gathers, tree and plane order are those of spmm_sliced_vec4_kernel: the sum of a row is taken in exactly
-// the same order, so the result is bit-identical to the fp32 product of the upcast table whenever both run with the same
-// rows per lane group and row chunks.  A lane owns 8 columns (one 16-B load per gathered row), so a lane group is half as
+// batches of 8 gathers, the canonical in-order row sum and the plane order are those of spmm_sliced_vec4_kernel, so the
+// result is bit-identical to the fp32 product of the upcast table, whatever the launch geometry of either.  A lane owns 8 columns (one 16-B load per gathered row), so a lane group is half as
 // wide as the fp32 kernel's for the same F.  No source-scale variant: the scale belongs to the conversion pass.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -69,30 +68,22 @@ __device__ __forceinline__ float4 widen(uint32_t u0, uint32_t u1) {
                      __uint_as_float(u1 & 0xffff0000u));
 }
 
-// One dword (2 columns) of a fast-path batch: widen, weight, the balanced tree of tree_sum (dgmi_segment.h) per column,
-// one add into the running sum.  Weighted, the fp32 kernel's `v *= w` + tree is contracted by the compiler into
-// fma(x[2k+1], w[2k+1], round(x[2k] * w[2k])) at the first tree level and plain adds above it; that arithmetic is spelled
-// out here (contraction off), so that the two kernels round alike: the bit-identity test holds both to it.
+// One dword (2 columns) of a fast-path batch: widen, and the canonical in-order sum of spmm_sliced_vec4_kernel
+// (acc = fmaf(w, x, acc) or acc + x, edge by edge) on each of the two columns.
 template <bool WEIGHTED, int K>
 __device__ __forceinline__ void batch_pair(const v4u (&raw)[kUnroll], const float (&w)[kUnroll], float& acc0, float& acc1) {
-#pragma clang fp contract(off)
-  float lo[kUnroll / 2], hi[kUnroll / 2];
 #pragma unroll
-  for (int k = 0; k < kUnroll / 2; ++k) {
-    const uint32_t e = raw[2 * k][K], o = raw[2 * k + 1][K];
-    const float le = __uint_as_float(e << 16), he = __uint_as_float(e & 0xffff0000u);
-    const float lo_ = __uint_as_float(o << 16), ho = __uint_as_float(o & 0xffff0000u);
+  for (int u = 0; u < kUnroll; ++u) {
+    const uint32_t d = raw[u][K];
+    const float lo = __uint_as_float(d << 16), hi = __uint_as_float(d & 0xffff0000u);
     if (WEIGHTED) {
-      lo[k] = __builtin_fmaf(lo_, w[2 * k + 1], le * w[2 * k]);
-      hi[k] = __builtin_fmaf(ho, w[2 * k + 1], he * w[2 * k]);
+      acc0 = fmaf(w[u], lo, acc0);
+      acc1 = fmaf(w[u], hi, acc1);
     } else {
-      lo[k] = le + lo_;
-      hi[k] = he + ho;
+      acc0 += lo;
+      acc1 += hi;
     }
   }
-  static_assert(kUnroll == 8, "the tree below is written for batches of 8");
-  acc0 += (lo[0] + lo[1]) + (lo[2] + lo[3]);
-  acc1 += (hi[0] + hi[1]) + (hi[2] + hi[3]);
 }
 
 // The gather of spmm_sliced_vec4_kernel (dgmi_sliced.hip) with 8 columns per lane: see there for the grid, KEEP and
@@ -104,9 +95,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR =
     const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ vals,
     const uint16_t* __restrict__ X, int64_t ldx, float* __restrict__ planes, int64_t ldp, int64_t n_dst, int64_t row_begin,
     int64_t row_end, int F, int n_slices, const int32_t* __restrict__ eid, const KeepSeg* __restrict__ keep, int n_keep,
-    int touch_lead, int rows_per_group, int touch_group) {
+    int touch_lead, SlicedRuns runs, int touch_group) {
   constexpr int G = kWave / LPR;
-  const int R = rows_per_group;  // < LPR: a group's row boundaries live one per lane
   constexpr bool HAS_VALS = VALS == 1;
   constexpr bool MULT = VALS == 2;
   constexpr bool WEIGHTED = HAS_VALS || MULT;
@@ -117,12 +107,13 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR =
   const int slice = (int)(blockIdx.x % (unsigned)n_slices);
   int64_t block = blockIdx.x / (unsigned)n_slices;
   if (touch_group > 0 &&
-      touch_ahead<LPR, HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, R, touch_lead, touch_group,
-                                       lane, wave, block))
+      touch_ahead<HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, runs, touch_lead, touch_group,
+                                  lane, wave, block))
     return;
-  const int64_t row0 = row_begin + ((block * kWavesPerBlock + wave) * G + grp) * R;
-  if (row0 >= row_end) return;  // whole group idle
-  const int nr = (int)(row0 + R <= row_end ? R : row_end - row0);
+  const SlicedRun run = sliced_run(runs, block, wave * G + grp);
+  const int nr = run.rows;  // < LPR: a group's row boundaries live one per lane
+  if (nr == 0) return;  // whole group idle
+  const int64_t row0 = row_begin + run.first;
   int col = ((int)blockIdx.y * LPR + glane) * 8;
   const bool col_ok = col < F;  // F % 8 == 0: all 8 columns or none
   if (!col_ok) col = 0;
@@ -175,8 +166,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR =
         raw[u] = ld_row8<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
         if (dropped) raw[u] = v4u{0u, 0u, 0u, 0u};  // a select, not 0 * x: Inf / NaN behind a dropped edge must not leak
       }
-      // fast path (group-uniform): all 8 edges belong to the current row -> balanced tree, no per-edge boundary tests;
-      // dword by dword: 16 widened values live at a time, not 64
+      // fast path (group-uniform): all 8 edges belong to the current row -> no per-edge boundary tests; dword by dword
       if (base + j + kUnroll <= next_b) {
         batch_pair<WEIGHTED, 0>(raw, w, acc_a.x, acc_a.y);
         __builtin_amdgcn_sched_barrier(0);  // one dword's 16 widened values at a time
@@ -241,7 +231,7 @@ hipError_t launch_sliced_bf16(const SlicedArgs& a, int64_t row_begin, int64_t ro
 #define DGMI_LAUNCH_O(V, K, O)                                                                                         \
   hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, V, K, O>), g.grid, block, 0, s, a.segptr, a.indices, a.vals,        \
                      static_cast<const uint16_t*>(a.X), a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, \
-                     (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.R,         \
+                     (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.runs,      \
                      g.touch_group)
 #define DGMI_LAUNCH(V, K)                                                    \
   do {                                                                       \

@@ -22,7 +22,8 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStrea
 namespace {
 
 constexpr int64_t kColumnPassMinRows = 32768;  // column passes only when a pass still has >= ~8k waves
-constexpr int kRowsPerGroup = 8;  // < LPR (row boundaries live one per lane of the group)
+constexpr int kRowsPerGroup = 8;  // < LPR (row boundaries live one per lane of the group); per width: rows_per_group
+constexpr int64_t kTaperRows = 8192;  // rows at the end of a chunk that take shorter runs (sliced_runs, sliced_geometry)
 constexpr int kTouchLead = 24;   // worker blocks of a slice between a toucher and the blocks it touches for
 constexpr int kTouchGroup = 8;   // worker blocks per toucher block
 
@@ -36,6 +37,58 @@ __device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
   __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
 }
 
+// Which destination rows a lane group sums.  A chunk's rows [0, n_rows) (relative to row_begin) are cut, in order, into
+// three sections of runs: the body in runs of `run[0]` = R rows, then — the tapered tail — the first half of the last
+// `taper` rows in runs of ceil(R / 2) and the second half in runs of ceil(R / 4), so that the blocks that start last are
+// the shortest-lived ones and the launch drains quickly.  A worker block takes `groups` (4 waves x G lane groups)
+// consecutive runs of ONE section; the last block of a section may be ragged.  The row sums do not depend on any of
+// this (canonical order, dgmi_sliced.hip), and the taper is a function of the row count alone: not of the width, the
+// slice or where the chunk lies.  sliced_runs is the host side (it also counts the blocks), sliced_run the mapping both
+// gather kernels, the touchers and the host test use; nothing else computes it.
+struct SlicedRuns {
+  int64_t end[3];     // chunk-relative row at which each section ends (end[2] = n_rows)
+  int64_t blocks[3];  // worker blocks up to the end of each section (blocks[2] = all worker blocks of a slice)
+  int run[3];         // rows per lane group in each section
+  int groups;         // lane groups per worker block
+};
+
+struct SlicedRun {
+  int64_t first;  // chunk-relative first row; n_rows when the group has nothing to do
+  int rows;
+};
+
+// `taper`: rows at the end of the chunk that take the shorter runs (clamped to [0, n_rows]).
+__host__ __device__ inline SlicedRuns sliced_runs(int64_t n_rows, int R, int G, int64_t taper) {
+  SlicedRuns t;
+  taper = taper < 0 ? 0 : (taper < n_rows ? taper : n_rows);
+  t.groups = kWavesPerBlock * G;
+  t.run[0] = R;
+  t.run[1] = (R + 1) / 2;
+  t.run[2] = (R + 3) / 4;
+  t.end[0] = n_rows - taper;
+  t.end[1] = n_rows - taper / 2;
+  t.end[2] = n_rows;
+  int64_t blocks = 0, begin = 0;
+  for (int s = 0; s < 3; ++s) {
+    const int64_t per_block = (int64_t)t.groups * t.run[s];
+    blocks += (t.end[s] - begin + per_block - 1) / per_block;
+    t.blocks[s] = blocks;
+    begin = t.end[s];
+  }
+  return t;
+}
+
+// The run of lane group `slot` (wave * G + group) of worker block `block` (numbered per slice, without the touchers).
+// Slot 0 of a block is never idle, so sliced_run(t, block, 0).first is the block's first row (n_rows past the last block).
+__host__ __device__ inline SlicedRun sliced_run(const SlicedRuns& t, int64_t block, int slot) {
+  const int s = block < t.blocks[0] ? 0 : (block < t.blocks[1] ? 1 : 2);
+  const int64_t begin = s > 0 ? t.end[s - 1] : 0, block0 = s > 0 ? t.blocks[s - 1] : 0;
+  const int64_t first = begin + ((block - block0) * t.groups + slot) * t.run[s];
+  if (block >= t.blocks[2] || first >= t.end[s]) return SlicedRun{t.end[2], 0};
+  const int64_t left = t.end[s] - first;
+  return SlicedRun{first, (int)(left < t.run[s] ? left : t.run[s])};
+}
+
 // Touch-ahead.  The id stream and the row boundaries are read once, so a wave's first two loads (boundaries, then
 // ids — dependent) miss every cache, and it gathers nothing for two memory latencies of its ~20 us life: inside a
 // training step, where the other products have pushed this one's ids out of the Infinity Cache, that is 10-25 % of the
@@ -43,22 +96,22 @@ __device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
 // lines (one word per 128-B line) of the touch_group worker blocks that start touch_lead worker blocks further on IN THE
 // SAME SLICE — same XCD, same L2, a few microseconds later — and leaves.  Nobody waits for these loads but the toucher
 // (vmcnt is in order: a worker that issued them would hold its own first gathers back).  A hint: results never depend on it.
+// The blocks it touches for are the worker blocks that really start there: their rows come from sliced_run.
 // `block`: this block's number within its slice, touchers included.  True: the block was a toucher and is done
 // (block-uniform); false: a worker, `block` renumbered without the touchers.
-template <int LPR, bool HAS_VALS, bool KEEP>
+template <bool HAS_VALS, bool KEEP>
 __device__ __forceinline__ bool touch_ahead(const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices,
                                             const float* __restrict__ vals, const int32_t* __restrict__ eid, int64_t n_dst,
-                                            int64_t row_begin, int64_t row_end, int slice, int R, int touch_lead,
-                                            int touch_group, int lane, int wave, int64_t& block) {
-  constexpr int G = kWave / LPR;
+                                            int64_t row_begin, int64_t row_end, int slice, const SlicedRuns& runs,
+                                            int touch_lead, int touch_group, int lane, int wave, int64_t& block) {
   const int64_t t = block / (touch_group + 1);
   if (block % (touch_group + 1) == 0) {
     __shared__ int range[2];
     const int32_t* sp_s = segptr + (int64_t)slice * n_dst;
-    const int64_t rows_blk = (int64_t)kWavesPerBlock * G * R;
-    const int64_t r_first = row_begin + (t * touch_group + touch_lead) * rows_blk;
+    const int64_t ahead = t * touch_group + touch_lead;
+    const int64_t r_first = row_begin + sliced_run(runs, ahead, 0).first;
     if (r_first >= row_end) return true;  // block-uniform
-    const int64_t r_last = min(r_first + touch_group * rows_blk, row_end);
+    const int64_t r_last = row_begin + sliced_run(runs, ahead + touch_group, 0).first;  // row_end past the last block
     int keepalive = 0;
     if (wave == 0) {  // lanes 0 / 1: the id range of those blocks; the others: one word per line of their boundaries
       const int64_t rp = lane == 0 ? r_first : (lane == 1 ? r_last : r_first + (int64_t)(lane - 1) * 32);
@@ -82,9 +135,23 @@ __device__ __forceinline__ bool touch_ahead(const int32_t* __restrict__ segptr, 
   return false;
 }
 
+// Rows per lane group, by lane-group width: a speed knob only (the sums do not depend on it).  The step of bench.py on
+// the canonical-order kernels, ms of the four half-width (16-lane, two-pass) products / of the four full-width (32-lane)
+// ones at 2 / 3 / 4 / 6 / 8 / 12 / 15 rows (profiles/sliced_tail/README.md):
+//   no taper      1.344 / 1.345 / 1.359 / 1.385 / 1.407 / 1.460 / 1.484     1.058 / 1.014 / 0.989 / 0.970 / 0.971 / 0.982 / 0.991
+//   taper 8192    1.351 / 1.330 / 1.333 / 1.338 / 1.338                     1.072 / 1.020 / 0.997 / 0.969 / 0.961
+// Without the taper the half-width products want 2-3 rows and the full-width ones 6-8 (what the short runs gave the
+// half-width products was mostly a shorter drain); with it 8 rows are within 0.01 ms — half a run-to-run spread of the
+// step — of the best value of either width at any taper, so one value serves every width.
+inline int rows_per_group(int lpr) {
+  (void)lpr;
+  return kRowsPerGroup;
+}
+
 // What one gather launch looks like on the host.
 struct SlicedGeometry {
-  int R;                // rows per lane group
+  int R;                // rows per lane group (the body's; the tapered tail's are shorter)
+  SlicedRuns runs;      // rows -> worker blocks and lane groups
   int64_t workers;      // worker blocks per slice
   int64_t touchers;     // toucher blocks per slice
   dim3 grid;            // x: n_slices * (workers + touchers); y: column tiles of lpr lanes
@@ -98,16 +165,22 @@ inline SlicedGeometry sliced_geometry(int64_t row_begin, int64_t row_end, int64_
                                       int64_t n_slices, int lpr, int elem_bytes) {
   SlicedGeometry g;
   const int G = kWave / lpr, cols = 16 / elem_bytes;
-  // Rows per lane group.  In the step (cold id stream, touch-ahead on), G edges/s at 4 / 6 / 8 / 12 / 15 rows: half-width
-  // products 31.8 / 31.2 / 30.8 / 28.2 / 27.9, full-width ones 28.4 / 29.5 / 30.1 / 30.2 / 30.3, the step 30.8 / 31.0 / 31.0 /
-  // 30.1 / 29.7.  One value for every width: where a group's run starts decides how its batches of 8 are cut, so a
-  // width-dependent value would make the column passes round differently from the full-width pass (they are bit-identical,
-  // test_xcd_sliced_column_passes).  Tuning::sliced_rows forces a value (tools).
+  // Rows per lane group and the tapered tail.  Both are speed knobs only: a row's sum does not depend on where its run
+  // starts (dgmi_sliced.hip).  Tuning::sliced_rows forces one value for every width, Tuning::sliced_taper_rows the
+  // taper's extent (-1: off) (tools, tests).
+  // The taper: a worker block lives ~55 us and a launch is only 2-4 rounds of blocks, so at the end of the grid every CU
+  // drains for most of a block life; with the last rows in runs of R / 2 and R / 4 the last blocks are short ones.  Step
+  // of bench.py at 8 rows, taper off / 2048 / 4096 / 8192 / 16384 / 32768 rows: 2.423 / 2.388 / 2.362 / 2.343 / 2.347 /
+  // 2.366 ms (profiles/sliced_tail/README.md).  Never more than a quarter of the chunk (not measured: short runs cost the
+  // full-width products up to 9 % when they cover all rows, the 2-row column above).
   const Tuning& tune = tuning();
-  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : kRowsPerGroup;
+  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : rows_per_group(lpr);
   g.R = rows_req < 1 ? 1 : (rows_req < lpr ? rows_req : lpr - 1);
-  const int64_t per_block = (int64_t)kWavesPerBlock * G * g.R;
-  g.workers = (row_end - row_begin + per_block - 1) / per_block;
+  const int64_t quarter = (row_end - row_begin) / 4;
+  const int64_t taper = tune.sliced_taper_rows < 0 ? 0
+                        : (tune.sliced_taper_rows > 0 ? tune.sliced_taper_rows : (kTaperRows < quarter ? kTaperRows : quarter));
+  g.runs = sliced_runs(row_end - row_begin, g.R, G, taper);
+  g.workers = g.runs.blocks[2];
   g.off32 = !tune.sliced_no_off32 && (n_src * ldx + F) * elem_bytes < ((int64_t)1 << 32);
   // Touch-ahead (see touch_ahead): one toucher per kTouchGroup worker blocks, kTouchLead worker blocks ahead.  An XCD starts
   // ~7 blocks of its slice per us, so 24 blocks are ~3.5 us of lead — a memory latency, and short enough for the touched

@@ -12,6 +12,7 @@ struct Tuning {
   int sliced_lpr = 0;               // DGMI_SLICED_LPR: lane-group width 8 / 16 / 32 / 64
   int sliced_no_off32 = 0;          // DGMI_NO_OFF32: 64-bit row addresses even where 32-bit offsets fit
   int64_t sliced_chunk_rows = 0;    // DGMI_SLICED_CHUNK_ROWS: destination rows per launch pair
+  int64_t sliced_taper_rows = 0;    // DGMI_SLICED_TAPER_ROWS: last rows of a chunk in shorter runs (-1: off, 0: built-in)
   int64_t select_window_min = 0;    // DGMI_SELECT_WINDOW_MIN: shortest list that takes the window passes
   int select_narrow_window = 0;     // DGMI_SELECT_NARROW_WINDOW: a window that misses (forces the take-over path; test)
   int sort_plain_tiles = 0;         // DGMI_SORT_PLAIN_TILES: record sort with tile = blockIdx.x instead of the XCD-aware order
