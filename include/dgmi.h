@@ -121,7 +121,9 @@ DGMI_API int dgmi_csr_from_coo_i32(const int32_t* row, const int32_t* col, int64
  * the layout builders) and `keep` holds n_keep (<= 8) eight-word descriptions written by
  * dgmi_random_subset_select (one per independently dropped edge list; several when a layout
  * concatenates relations).  Dropped edges are skipped — their source rows are not read into the
- * sum, so Inf / NaN there do not leak (unlike a 0/1 value mask).  n_keep == 0: eid, keep unused.
+ * sum, so Inf / NaN there do not leak (unlike a 0/1 value mask).  This covers source ROWS only:
+ * `vals` and `src_scale` must be finite for every edge, dropped ones included (a dropped edge's
+ * zeroed row is still multiplied by its weight).  n_keep == 0: eid, keep unused.
  *
  * Output epilogue (all three SpMM entry points), fused into the kernel that writes Y —
  * GCMCLayer's `dropout(agg_act(...))` on the aggregated messages (layers.py:134-138):
