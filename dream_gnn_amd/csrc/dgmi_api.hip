@@ -36,6 +36,12 @@ Tuning& tuning() {
     v.sliced_no_off32 = getenv("DGMI_NO_OFF32") != nullptr ? 1 : 0;
     v.sliced_chunk_rows = env_ll("DGMI_SLICED_CHUNK_ROWS", 0);
     v.sliced_taper_rows = env_ll("DGMI_SLICED_TAPER_ROWS", 0);
+    v.sliced_owned = (int)env_ll("DGMI_SLICED_OWNED", -1);
+    v.sliced_owned_grid = (int)env_ll("DGMI_SLICED_OWNED_GRID", 0);
+    v.sliced_owned_rows = (int)env_ll("DGMI_SLICED_OWNED_ROWS", 0);
+    v.sliced_owned_lds_rows = env_ll("DGMI_SLICED_OWNED_LDS_ROWS", 0);
+    v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
+    v.sliced_owned_spin_ticks = env_ll("DGMI_SLICED_OWNED_SPIN_TICKS", 0);
     v.select_window_min = env_ll("DGMI_SELECT_WINDOW_MIN", 0);
     v.select_narrow_window = env_ll("DGMI_SELECT_NARROW_WINDOW", 0) != 0 ? 1 : 0;
     v.sort_plain_tiles = env_ll("DGMI_SORT_PLAIN_TILES", 0) != 0 ? 1 : 0;
@@ -59,6 +65,12 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_no_off32") == 0) t.sliced_no_off32 = value != 0;
   else if (strcmp(name, "sliced_chunk_rows") == 0) t.sliced_chunk_rows = value;
   else if (strcmp(name, "sliced_taper_rows") == 0) t.sliced_taper_rows = value;
+  else if (strcmp(name, "sliced_owned") == 0) t.sliced_owned = (int)value;
+  else if (strcmp(name, "sliced_owned_grid") == 0) t.sliced_owned_grid = (int)value;
+  else if (strcmp(name, "sliced_owned_rows") == 0) t.sliced_owned_rows = (int)value;
+  else if (strcmp(name, "sliced_owned_lds_rows") == 0) t.sliced_owned_lds_rows = value;
+  else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;
+  else if (strcmp(name, "sliced_owned_spin_ticks") == 0) t.sliced_owned_spin_ticks = value;
   else if (strcmp(name, "select_window_min") == 0) t.select_window_min = value;
   else if (strcmp(name, "select_narrow_window") == 0) t.select_narrow_window = value != 0;
   else if (strcmp(name, "sort_plain_tiles") == 0) t.sort_plain_tiles = value != 0;

@@ -1,0 +1,117 @@
+// dgmi_owned_common.h — the plan of the workgroup-owned form of the XCD-local SpMM (dgmi_owned.hip): which destination
+// rows a workgroup owns, how they are cut into rounds that fit its LDS, and which rows a task of a phase sums.  The
+// kernel, its launcher and the host test (tests/test_owned_plan_host.py) use owned_plan / owned_phase / owned_task and
+// nothing else.
+//
+// Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
+// column tile (16 LPR bytes) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
+// (column round, row round, slice), slices 0 .. 7 innermost and in order: the row sums take their 8 segment sums in the
+// order the plane reduce adds the planes.  A phase is cut into TASKS of G R consecutive rows of the round — one wave,
+// R rows for each of its G = 64 / LPR lane groups; task t of every phase of a round covers the same LDS rows.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace dgmi {
+
+constexpr int kOwnedSlices = 8;                     // the form exists for 8 slices only (one per XCD)
+constexpr int kOwnedWaves = 16;                     // waves per workgroup: 15 workers and the toucher
+constexpr int kOwnedWorkers = kOwnedWaves - 1;
+constexpr int64_t kOwnedLdsRowBytes = 144 << 10;    // LDS budget of the partial rows (the CU has 160 KiB)
+constexpr int kOwnedMaxPhases = 128;                // per-phase words live in LDS and in the arrive counters
+constexpr int kOwnedPhaseTasks = 24;                // built-in R aims at this many tasks per phase
+constexpr int kOwnedMaxRows = 8;                    // built-in upper bound of R
+
+struct OwnedPlan {
+  bool ok;             // false: the form does not take this product (too many phases, nothing to do)
+  int lpr, G, R;       // lane-group width, lane groups per wave, rows per lane group and task
+  int col_rounds, row_rounds, phases;
+  int64_t wg_rows;     // B
+  int64_t active;      // workgroups that own at least one row: 0 .. active - 1
+  int round_rows;      // rows of a workgroup in one row round = LDS rows
+  int tasks;           // task slots per phase of a workgroup that owns B rows
+  int64_t n_dst;
+  size_t lds_bytes;    // partial rows, then tasks + phases + 2 control words
+};
+
+struct OwnedPhase {
+  int col_round, row_round, slice;
+};
+
+struct OwnedTask {
+  int64_t row0;  // first destination row of the lane group
+  int lds_row;   // its LDS row
+  int rows;      // 0: nothing to do
+};
+
+// `lpr`: lane-group width (sliced_lpr); `R_req` <= 0: built-in — about kOwnedPhaseTasks tasks per phase, 1.6 per worker
+// wave (measured, profiles/owned_rows/README.md: fewer, longer tasks leave waves idle at the end of a phase, more and
+// shorter ones pay the start of a task — boundaries, then ids, then the first gathers — too often; a task still
+// practically never waits for its predecessor of the phase before); `lds_rows_cap` > 0: at most that many LDS rows
+// (forces row rounds).
+__host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap) {
+  OwnedPlan p{};
+  p.ok = false;
+  p.n_dst = n_dst;
+  if (n_dst < 1 || F < 1 || grid < 1 || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64)) return p;
+  p.lpr = lpr;
+  p.G = 64 / lpr;
+  p.col_rounds = (int)((F + 4 * lpr - 1) / (4 * lpr));
+  p.wg_rows = (n_dst + grid - 1) / grid;
+  p.active = (n_dst + p.wg_rows - 1) / p.wg_rows;
+  int64_t fit = kOwnedLdsRowBytes / (16 * lpr);
+  if (lds_rows_cap > 0 && lds_rows_cap < fit) fit = lds_rows_cap;
+  const int64_t rounds = (p.wg_rows + fit - 1) / fit;
+  if (rounds * p.col_rounds * kOwnedSlices > kOwnedMaxPhases) return p;
+  p.row_rounds = (int)rounds;
+  p.round_rows = (int)((p.wg_rows + rounds - 1) / rounds);  // <= fit
+  p.phases = p.col_rounds * p.row_rounds * kOwnedSlices;
+  int R = R_req;
+  if (R <= 0) {
+    R = (p.round_rows + kOwnedPhaseTasks * p.G / 2) / (kOwnedPhaseTasks * p.G);  // rounded to nearest
+    if (R > kOwnedMaxRows) R = kOwnedMaxRows;
+  }
+  if (R > lpr - 1) R = lpr - 1;  // a group's row boundaries live one per lane
+  if (R < 1) R = 1;
+  p.R = R;
+  p.tasks = (p.round_rows + p.G * R - 1) / (p.G * R);
+  p.lds_bytes = (size_t)p.round_rows * 16 * lpr + sizeof(int) * ((size_t)p.tasks + p.phases + 2);
+  p.ok = true;
+  return p;
+}
+
+// Rows workgroup `wg` owns (the last active one may own fewer; the ones after it none).
+__host__ __device__ inline int64_t owned_wg_rows(const OwnedPlan& p, int64_t wg) {
+  const int64_t left = p.n_dst - wg * p.wg_rows;
+  return left < 0 ? 0 : (left < p.wg_rows ? left : p.wg_rows);
+}
+
+// Rows of workgroup `wg` in row round `row_round` (0 for a round a short workgroup does not reach).
+__host__ __device__ inline int64_t owned_round_rows(const OwnedPlan& p, int64_t wg, int row_round) {
+  const int64_t left = owned_wg_rows(p, wg) - (int64_t)row_round * p.round_rows;
+  return left < 0 ? 0 : (left < p.round_rows ? left : p.round_rows);
+}
+
+// Task slots per phase of workgroup `wg`: the same in every phase (a slot whose rows a short last round does not have
+// is an empty task), 0 for a workgroup without rows.
+__host__ __device__ inline int owned_wg_tasks(const OwnedPlan& p, int64_t wg) {
+  int64_t rows = owned_wg_rows(p, wg);
+  if (rows > p.round_rows) rows = p.round_rows;
+  return (int)((rows + p.G * p.R - 1) / (p.G * p.R));
+}
+
+__host__ __device__ inline OwnedPhase owned_phase(const OwnedPlan& p, int phase) {
+  const int cq = phase / kOwnedSlices;
+  return OwnedPhase{cq / p.row_rounds, cq % p.row_rounds, phase % kOwnedSlices};
+}
+
+// Lane group `group` (0 .. G - 1) of task slot `task` in row round `row_round` of workgroup `wg`.
+__host__ __device__ inline OwnedTask owned_task(const OwnedPlan& p, int64_t wg, int row_round, int task, int group) {
+  const int64_t lds_row = ((int64_t)task * p.G + group) * p.R;
+  int64_t rows = owned_round_rows(p, wg, row_round) - lds_row;
+  rows = rows < 0 ? 0 : (rows < p.R ? rows : p.R);
+  return OwnedTask{wg * p.wg_rows + (int64_t)row_round * p.round_rows + lds_row, (int)lds_row, (int)rows};
+}
+
+}  // namespace dgmi

@@ -42,17 +42,6 @@ namespace {
 // bit of its source id; its gather repeats the group's previous row (an L1 hit — never one fixed row,
 // which would turn 10 % of all gathers into traffic on a single L2 channel) and its contribution is
 // replaced by zeros.
-// Source row `idx` of the feature table.  OFF32: the table is < 4 GiB, so the byte offset fits 32 bits — one
-// v_mul_lo_u32 and a global_load with a scalar base and a 32-bit vector offset, instead of the six-instruction 64-bit
-// multiply-add chain a (int64 ldx) product costs per gathered row.
-template <bool OFF32>
-__device__ __forceinline__ float4 ld_row(const float* __restrict__ X, const float* __restrict__ Xc, int idx, int64_t ldx,
-                                         uint32_t row_bytes, uint32_t col_bytes) {
-  // X is the (wave-uniform) table base, Xc = X + this lane's column
-  if (OFF32) return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
-  return ld4(Xc + (int64_t)idx * ldx);
-}
-
 // VALS: 0 = unit edge values; 1 = vals[p]; 2 = small integer multiplicities carried in the id words themselves (bits
 // kMultShift..30 hold m - 1): the reference's adjacencies are D^-1 (A + A^T + I) (data_loader.py:297-308, utils.py:11-17),
 // i.e. value = row scale x multiplicity — the scale goes where dst_scale / src_scale go, the multiplicity rides with the
@@ -342,6 +331,9 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStrea
 
 hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s) {
   if (a.x_bytes != 4) return hipErrorInvalidValue;
+  bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip)
+  const hipError_t err = spmm_owned_try(a, s, &owned);
+  if (err != hipSuccess || owned) return err;
   return spmm_sliced_chunks(a, launch_gather_f32, s);
 }
 

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restri
 }
 
 // Source row `idx` of the bf16 table: this lane's 8 columns, one 16-B load.  OFF32: the table is < 4 GiB (see ld_row of
-// dgmi_sliced.hip).
+// dgmi_sliced_common.h).
 template <bool OFF32>
 __device__ __forceinline__ v4u ld_row8(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Xc, int idx, int64_t ldx,
                                        uint32_t row_bytes, uint32_t col_bytes) {

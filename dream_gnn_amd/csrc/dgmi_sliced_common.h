@@ -19,6 +19,10 @@ typedef hipError_t (*SlicedGather)(const SlicedArgs& a, int lpr, int64_t row_beg
 // (sliced_lpr below), runs `gather` and then the plane reduce with the chunk's dst_scale / Y / mask offsets.
 hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStream_t s);
 
+// The workgroup-owned form (dgmi_owned.hip): rows summed in LDS, no planes, bit-identical to the pair.  *taken: the
+// product was launched; false (and hipSuccess): the form does not take it and the caller runs the pair.
+hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken);
+
 namespace {
 
 constexpr int64_t kColumnPassMinRows = 32768;  // column passes only when a pass still has >= ~8k waves
@@ -35,6 +39,17 @@ __device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
   // (ordinary stores instead: the step of bench.py 3.03 ms against 2.85 ms, profiles/r03_swept_experiment/)
   v4f t = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
+}
+
+// Source row `idx` of the feature table.  OFF32: the table is < 4 GiB, so the byte offset fits 32 bits — one
+// v_mul_lo_u32 and a global_load with a scalar base and a 32-bit vector offset, instead of the six-instruction 64-bit
+// multiply-add chain a (int64 ldx) product costs per gathered row.
+template <bool OFF32>
+__device__ __forceinline__ float4 ld_row(const float* __restrict__ X, const float* __restrict__ Xc, int idx, int64_t ldx,
+                                         uint32_t row_bytes, uint32_t col_bytes) {
+  // X is the (wave-uniform) table base, Xc = X + this lane's column
+  if (OFF32) return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
+  return ld4(Xc + (int64_t)idx * ldx);
 }
 
 // Which destination rows a lane group sums.  A chunk's rows [0, n_rows) (relative to row_begin) are cut, in order, into

@@ -13,6 +13,12 @@ struct Tuning {
   int sliced_no_off32 = 0;          // DGMI_NO_OFF32: 64-bit row addresses even where 32-bit offsets fit
   int64_t sliced_chunk_rows = 0;    // DGMI_SLICED_CHUNK_ROWS: destination rows per launch pair
   int64_t sliced_taper_rows = 0;    // DGMI_SLICED_TAPER_ROWS: last rows of a chunk in shorter runs (-1: off, 0: built-in)
+  int sliced_owned = -1;            // DGMI_SLICED_OWNED: the workgroup-owned form (dgmi_owned.hip) 0 = never, 1 = whenever applicable, -1 = built-in rule
+  int sliced_owned_grid = 0;        // DGMI_SLICED_OWNED_GRID: its workgroups (0: one per CU)
+  int sliced_owned_rows = 0;        // DGMI_SLICED_OWNED_ROWS: rows per lane group and task (0: built-in)
+  int64_t sliced_owned_lds_rows = 0;  // DGMI_SLICED_OWNED_LDS_ROWS: cap on a workgroup's LDS rows (forces row rounds; 0: the LDS budget)
+  int sliced_owned_lag = -2;        // DGMI_SLICED_OWNED_LAG: phases a workgroup may run ahead of its XCD's slowest (-1: no gate, -2: built-in)
+  int64_t sliced_owned_spin_ticks = 0;  // DGMI_SLICED_OWNED_SPIN_TICKS: bound of one gate wait, 100 MHz ticks (0: built-in)
   int64_t select_window_min = 0;    // DGMI_SELECT_WINDOW_MIN: shortest list that takes the window passes
   int select_narrow_window = 0;     // DGMI_SELECT_NARROW_WINDOW: a window that misses (forces the take-over path; test)
   int sort_plain_tiles = 0;         // DGMI_SORT_PLAIN_TILES: record sort with tile = blockIdx.x instead of the XCD-aware order
