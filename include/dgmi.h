@@ -385,8 +385,9 @@ DGMI_API int dgmi_compact_layout_i32(const int32_t* ptr, int64_t n_ptr, const in
  * with fp32 MFMA (exact f32 fma chains) and reduced to a running top-k on chip; nothing of size
  * N x N is written.  From N = 1536 rows the candidates are first screened on the bf16 matrix cores
  * with a rounding bound that provably keeps every member of the fp32 top-k, then rescored in fp32
- * (rows must be unit vectors or zero for that bound).  Ties at the k-th value are broken arbitrarily
- * (upstream too).
+ * (rows must be unit vectors or zero for that bound).  A zero row has similarity 0 to every row, itself
+ * included, so its list is the usual top-k of a row of zeros and its own id is not necessarily first (or
+ * present).  Ties at the k-th value are broken arbitrarily (upstream too).
  * dgmi_knn_cosine_supported: 1 if the shape fits the kernels (D % 8 == 0, k <= N, k <= 16 — or k <= 64 when
  * N >= 1536 and D <= 1024, where the bf16 screen runs and a wave's lanes hold the top-k —, the 32-query
  * tile + lists within LDS: D <= 1024 for k <= 4, D <= 896 for k = 16); callers fall back otherwise.

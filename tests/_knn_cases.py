@@ -1,5 +1,7 @@
 """Designed rows for the bf16-screened cosine kNN (csrc/dgmi_knn_screen.hip), and the screen's arithmetic restated on the
-host.  Plain module (like _rank_cases.py), shared by test_knn_cases_host.py, test_gpu_spmm.py and tools/knn_soak.py.
+host.  Plain module (like _rank_cases.py), shared by test_knn_cases_host.py, test_gpu_spmm.py and tools/knn_soak.py; its
+second half (unit rows on a lattice, the screen's workspace layout and emission regions restated) serves
+test_knn_lattice_host.py and test_gpu_knn_exact.py.
 
 The screen multiplies bf16 copies of unit rows (round to nearest even: unit roundoff 2**-8 per element) and keeps every
 candidate within ``2 * eps`` of a lower bound of the query's k-th best approximate score; the answer is exact only if
@@ -18,6 +20,7 @@ rescoring once k decoys B_j have set the threshold.
 
 eta = 2**-18 survives the rounding of the designed values to fp32 (half an ulp is 2**-24 relative) and is far below what
 the scores resolve."""
+import functools
 import math
 from collections import namedtuple
 
@@ -116,3 +119,238 @@ def embed(base, design, q_at, a_at, b_at=0):
     assert len({q_at, a_at} | set(range(b_at, b_at + k))) == k + 2
     x[q_at], x[a_at], x[b_at:b_at + k] = design.q, design.A, design.B
     return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Unit rows on a lattice: every similarity exact in every number format and summation order of the search.
+#
+# A row has exactly nz = 4**m non-zeros, each +-2**-m (nz = 64, +-1/8 for D >= 128; nz = 16, +-1/4 for D = 64): its fp32
+# norm is exactly 1, every element is a bf16 number, every dot product is an integer multiple of 1 / nz in [-1, 1] whose
+# partial sums are multiples of 1 / nz too — the fp32 MFMA chain, the bf16 screen and the rescoring's `wave_dot` return the
+# same value, and the reference is an integer matrix product (`Lattice.num`: the numerators -1 / 0 / +1 of the elements).
+#   ordinary   nz / 4 anchor columns (0 .. nz / 4 - 1) all +, the other 3 nz / 4 at random columns with random signs:
+#              similarity 1/4 + a small random part to each other — few levels, so the k-th boundary cuts a tie class
+#   antipodal  the anchors all -: similarity -1/4 + a small random part to every ordinary row; their k-th neighbour is
+#              negative once k passes their few non-negative candidates (self, the other antipodal rows, the zero rows)
+#   zero       all-zero rows (what `feature_similarity_graph` makes of a zero-norm feature row): similarity 0 to everything
+#   block      `block` exact copies of one ordinary row, contiguous, across a 128- and a 256-row boundary (and 32-row ones)
+#   pairs      scattered exact copies of single ordinary rows
+# Special rows sit at the front (ids < 32: the first tile of every kernel), around 2 N / 3 and among the last five rows.
+Lattice = namedtuple("Lattice", "N D nz x num antipodal zero block pairs")
+
+
+def lattice_nz(D):
+    return 64 if D >= 128 else 16
+
+
+@functools.lru_cache(maxsize=None)
+def lattice(N, D, seed=3, specials=True, block=None):
+    """The rows described above.  `specials=False`: ordinary rows and the block only.  `block`: copies in the block
+    (default 300 from 700 rows, N / 4 below).  Returns x (N, D) float32, num (N, D) int8, the ids of the special rows,
+    the block as (lo, hi) and the pairs as (original, copy)."""
+    assert D >= 64 and N >= 16
+    nz = lattice_nz(D)
+    anchors, rest = nz // 4, nz - nz // 4
+    rng = np.random.default_rng(seed)
+    num = np.zeros((N, D), dtype=np.int8)
+    num[:, :anchors] = 1
+    cols = anchors + np.argpartition(rng.random((N, D - anchors), dtype=np.float32), rest, axis=1)[:, :rest]
+    np.put_along_axis(num, cols, (rng.integers(0, 2, (N, rest)) * 2 - 1).astype(np.int8), axis=1)
+    if block is None:
+        block = 300 if N >= 700 else N // 4
+    if N >= 700:
+        lo = 256 * max(1, (N // 4 + 128) // 256) - 150       # straddles a multiple of 256 (and of 128 on either side)
+    else:
+        lo = min(32, N // 2) - block // 2                    # straddles row 32 (tiny N: row N / 2)
+    assert 0 <= lo and lo + block <= N
+    num[lo:lo + block] = num[lo]
+    antipodal, zero, pairs = (), (), ()
+    if specials:
+        mid = 2 * N // 3
+        if N >= 64:
+            antipodal, zero = (5, mid + 5, N - 2), (9, 10, mid + 9, N - 3, N - 1)
+            pairs = ((12, mid + 12), (mid + 14, N - 4), (14, N - 5))
+        else:
+            antipodal, zero, pairs = (1,), (2, N - 1), ((3, N - 2),)
+        used = list(antipodal + zero) + [i for p in pairs for i in p]
+        assert len(set(used)) == len(used) and all(0 <= i < N and not lo <= i < lo + block for i in used)
+        for a, b in pairs:
+            num[b] = num[a]
+        for i in antipodal:
+            num[i, :anchors] = -1
+        for i in zero:
+            num[i] = 0
+    x = torch.from_numpy(num.astype(np.float32) * np.float32(1.0 / math.sqrt(nz)))
+    num.setflags(write=False)
+    return Lattice(N, D, nz, x, num, antipodal, zero, (lo, lo + block), pairs)
+
+
+@functools.lru_cache(maxsize=None)
+def mostly_zero(N, D, live=64, seed=3):
+    """All rows zero except `live` lattice rows spread evenly: every query's threshold is <= 0, so every region of every
+    query overflows and the whole answer comes from the exact take-over."""
+    base = lattice(N, D, seed, specials=False)
+    keep = np.linspace(0, N - 1, live).astype(np.int64)
+    num = np.zeros_like(base.num)
+    num[keep] = base.num[keep]
+    num.setflags(write=False)
+    zero = tuple(sorted(set(range(N)) - set(keep.tolist())))
+    x = torch.from_numpy(num.astype(np.float32) * np.float32(1.0 / math.sqrt(base.nz)))
+    return Lattice(N, D, base.nz, x, num, (), zero, (0, 0), ())
+
+
+def similarity_numerators(num, rows=None):
+    """S[i, j] * nz as int64 (exact), for the query rows `rows` (default all) against every row."""
+    a = num if rows is None else num[np.asarray(rows)]
+    return (a.astype(np.float32) @ num.astype(np.float32).T).astype(np.int64)   # |sums| <= 64: exact in fp32 in any order
+
+
+def expected_topk(S, k):
+    """Ids of the k best candidates of every row of S by (similarity descending, id ascending)."""
+    return np.argsort(-np.asarray(S), axis=1, kind="stable")[:, :k]
+
+
+# --- the small-N kernel's candidate splits and the screen's workspace, restated (dgmi_knn.hip, dgmi_knn_screen.hip) ---
+SCREEN_MIN_ROWS, SCREEN_BIG_MIN_ROWS, SPLITS, POOL_CHUNK = 1536, 49152, 8, 256
+SCREEN_EPS = np.float32(0.008)
+OVERFLOW_MARK = 0x40000000
+
+ScreenLayout = namedtuple("ScreenLayout", "big sym tile Np Dp cap_r cap_c pool_chunks xb part tau thr cnt buf flags pool "
+                                          "pool_ctl total")
+
+
+def knn_splits(N):
+    """`knn_splits`: (splits, 32-candidate tiles per split) of the fp32 kernel below the screen's crossover."""
+    q_tiles = c_tiles = (N + 31) // 32
+    s = max(1, min((512 + q_tiles - 1) // q_tiles, (c_tiles + 3) // 4, 64))
+    return s, (c_tiles + s - 1) // s
+
+
+def _align256(b):
+    return (b + 255) & ~255
+
+
+def default_pool_chunks(N, k):
+    """The built-in `knn_pool_chunks` of the 256 x 256 shape: room for 20 k + 112 records per query in 256-record chunks,
+    plus one partly filled chunk per wave of every workgroup in flight."""
+    return min((N * (20 * k + 112) + POOL_CHUNK - 1) // POOL_CHUNK + 2048, 1 << 30)
+
+
+def screen_layout(N, D, k, pool_chunks=0):
+    """`screen_layout`: tile shape, sweep, padded sizes, region caps, pool chunks (`pool_chunks` > 0: the tuning knob) and the
+    byte offset of every array in the workspace, each rounded up to 256 bytes."""
+    big = N >= SCREEN_BIG_MIN_ROWS
+    tile = 256 if big else 128
+    Np, Dp = (N + tile - 1) // tile * tile, (D + 63) // 64 * 64
+    sym = N >= (24576 if k <= 8 else 40960)
+    cap_r = 128 if k <= 8 else (256 if (k <= 16 or sym) else 512)
+    cap_c = SPLITS * cap_r if sym else 0
+    chunks = default_pool_chunks(N, k) if big else 0
+    if chunks and pool_chunks > 0:
+        chunks = pool_chunks
+    at, offs = 0, []
+    for size in (Np * Dp * 2, N * 64 * 4 * 4, N * 4, Np * 4, N * (SPLITS + 1) * 4, N * (SPLITS * cap_r + cap_c) * 8, N * 4,
+                 chunks * POOL_CHUNK * 16, (chunks + 1) * 4 if chunks else 0):
+        offs.append(at)
+        at += _align256(size)
+    return ScreenLayout(big, sym, tile, Np, Dp, cap_r, cap_c, chunks, *offs, at)
+
+
+def workspace_bytes(N, D, k, pool_chunks=0):
+    """`dgmi_knn_cosine_workspace_bytes` for a supported shape."""
+    if N >= SCREEN_MIN_ROWS and D <= 1024:
+        return screen_layout(N, D, k, pool_chunks).total
+    s, _ = knn_splits(N)
+    return 0 if s == 1 else s * N * k * 8
+
+
+def emit_tile_ranges(N, k, q_tile):
+    """The candidate tiles [t0, t1) of the 8 workgroups (splits) that emit for query tile `q_tile`: contiguous ranges of
+    ceil(remaining / 8) tiles, from tile 0 on the full rectangle and from the diagonal tile under the triangular sweep."""
+    L = screen_layout(N, 64, k)
+    n_tiles = L.Np // L.tile
+    first = q_tile if L.sym else 0
+    per = (n_tiles - first + SPLITS - 1) // SPLITS
+    out = []
+    for s in range(SPLITS):
+        t0 = first + s * per
+        out.append((t0, t0 + (per if t0 + per <= n_tiles else max(n_tiles - t0, 0))))
+    return out
+
+
+def emit_regions(N, k, q):
+    """Where query q's buffer entries come from: ([lo, hi) candidate ids of its 8 row regions, [0, hi) of its column
+    region).  A row region takes every candidate of its split's tiles, the diagonal tile whole (self included); the column
+    region (triangular sweep) takes what the query tiles BEFORE q's own offer, i.e. the candidates in front of q's tile."""
+    L = screen_layout(N, 64, k)
+    qt = q // L.tile
+    rows = [(min(t0 * L.tile, N), min(t1 * L.tile, N)) for t0, t1 in emit_tile_ranges(N, k, qt)]
+    return rows, (0, qt * L.tile if L.sym else 0)
+
+
+def region_counts(S, q_ids, thr, N, k):
+    """(len(q_ids), 9) entries offered to the 8 row regions and the column region of the queries `q_ids`, whose rows of
+    similarities are S (len(q_ids), N), under the per-query emission thresholds `thr` (same unit as S)."""
+    hit = np.asarray(S) >= np.asarray(thr)[:, None]
+    run = np.concatenate([np.zeros((hit.shape[0], 1), dtype=np.int64), np.cumsum(hit, axis=1)], axis=1)
+    out = np.zeros((len(q_ids), SPLITS + 1), dtype=np.int64)
+    for i, q in enumerate(q_ids):
+        rows, col = emit_regions(N, k, int(q))
+        out[i, :SPLITS] = [run[i, hi] - run[i, lo] for lo, hi in rows]
+        out[i, SPLITS] = run[i, col[1]] - run[i, col[0]]
+    return out
+
+
+def region_caps(N, k):
+    L = screen_layout(N, 64, k)
+    return np.array([L.cap_r] * SPLITS + [L.cap_c], dtype=np.int64)
+
+
+def pessimistic_threshold(S, k, nz, tile):
+    """The lowest emission threshold the k <= 4 sample can produce, in numerators: each lane keeps its four best, so tau' is
+    the exact k-th largest over the sampled candidates, and candidate tile 0 is always sampled — tau' >= the k-th largest
+    inside tile 0.  Minus 2 eps = 0.016 (just over one lattice step at nz = 64)."""
+    assert k <= 4
+    kth = -np.sort(-np.asarray(S)[:, :tile], axis=1)[:, k - 1]
+    tau = (kth / nz).astype(np.float32)
+    return (tau - np.float32(2.0) * SCREEN_EPS).astype(np.float64) * nz
+
+
+def sampled_tiles(N, D, k, screen_first=False):
+    """The candidate tiles the SAMPLE pass multiplies: every `stride`-th tile (8 from 64 tiles, n_tiles / 8 below, every
+    tile below 8; the LDS-DMA kernel: 4 for k > 16 from 128 tiles), dealt round-robin to the 8 splits; the LDS-DMA kernel
+    (256 x 256 tiles, two or more 64-column chunks, not `knn_screen_first`) gives every split the same number of tiles
+    and leaves the few beyond a multiple of 8 out.  Tile 0 is always among them."""
+    L = screen_layout(N, D, k)
+    n_tiles = L.Np // L.tile
+    dma = L.big and L.Dp >= 128 and not screen_first
+    stride = 4 if dma and k > 16 and n_tiles >= 128 else (8 if n_tiles >= 64 else (n_tiles // 8 if n_tiles >= 8 else 1))
+    out = []
+    for s in range(SPLITS):
+        t0, step = stride * s, stride * SPLITS
+        nt = (n_tiles - t0 + step - 1) // step if n_tiles > t0 else 0
+        sampled = (n_tiles + stride - 1) // stride
+        if dma and sampled >= 2 * SPLITS:
+            nt = min(nt, sampled // SPLITS)
+        out += [t0 + step * i for i in range(nt)]
+    return sorted(out), L.tile
+
+
+def sample_threshold(S, N, D, k, nz, screen_first=False):
+    """(tau', emission threshold) in numerators for k <= 4, where every lane's four best hold the k best of its subset and
+    tau' is the exact k-th largest over the sampled candidates."""
+    assert k <= 4
+    tiles, T = sampled_tiles(N, D, k, screen_first)
+    cols = np.concatenate([np.arange(t * T, min((t + 1) * T, N)) for t in tiles])
+    kth = -np.sort(-np.asarray(S)[:, cols], axis=1)[:, k - 1]
+    tau = (kth / nz).astype(np.float32)
+    return kth, (tau - np.float32(2.0) * SCREEN_EPS).astype(np.float64) * nz
+
+
+# (N, D, k) of tests/test_gpu_knn_exact.py, the smallest N at which each path exists (test_knn_lattice_host.py checks the
+# designs at exactly these shapes)
+SMALL_SHAPES = [(763, 256, 4), (1500, 128, 13), (1535, 64, 16), (97, 64, 13), (33, 64, 16), (16, 64, 16)]
+RECT_SHAPES = [(N, D, k) for N in (1536, 2048 + 37) for D, k in ((256, 4), (256, 13), (256, 40), (256, 64), (64, 4), (768, 4))]
+TRI_SHAPES = [(24576 + 128 + 37, 256, 4), (40960 + 37, 256, 12), (40960 + 37, 256, 64)]
+BIG_SHAPES = [(49152 + 300, 256, 4), (49152 + 300, 256, 12), (49152 + 300, 256, 40), (49152 + 300, 64, 4)]
+SCREEN_SHAPES = RECT_SHAPES + TRI_SHAPES + BIG_SHAPES
