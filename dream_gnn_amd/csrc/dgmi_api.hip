@@ -235,6 +235,12 @@ static int64_t slice_width_for(int64_t n_cols, int32_t n_slices) {
   return w > 0 ? w : 1;
 }
 
+static int id_bits(int64_t n) {  // bits_for of dgmi_csr.hip: the bits the ids 0 .. n - 1 take, at least 1
+  int b = 1;
+  while (b < 32 && ((int64_t)1 << b) < n) ++b;
+  return b;
+}
+
 DGMI_API int dgmi_csr_sliced_from_coo_i32(const int32_t* row, const int32_t* col, int64_t E, int64_t n_rows,
                                           int64_t n_cols, int32_t n_slices, int32_t* segptr,
                                           int32_t* indices, int32_t* eid, void* workspace,
@@ -268,6 +274,9 @@ DGMI_API int dgmi_csr_sliced_from_csr_i32(const int32_t* indptr, const int32_t* 
   if (E < 0 || n_rows < 0 || n_cols < 0 || n_slices < 1 || n_slices > 64 || workspace_bytes == nullptr)
     return DGMI_ERR_INVALID_ARG;
   if (E > INT32_MAX || n_cols >= INT32_MAX || n_rows * (int64_t)n_slices >= INT32_MAX) return DGMI_ERR_TOO_LARGE;
+  // the position key is (slice << row_bits) | row in an int32 that the boundary pass decodes with an arithmetic shift:
+  // with 32 key bits the upper slices would read as negative.  (The COO builder's key is slice * n_rows + row.)
+  if (id_bits(n_rows) + id_bits(n_slices) > 31) return DGMI_ERR_TOO_LARGE;
   if (workspace != nullptr) {
     if (segptr == nullptr) return DGMI_ERR_INVALID_ARG;
     if (E > 0 && (indptr == nullptr || indices == nullptr || eid == nullptr || s_indices == nullptr || s_eid == nullptr))

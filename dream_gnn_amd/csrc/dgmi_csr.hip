@@ -250,7 +250,7 @@ hipError_t csr_sliced_from_csr_i32(const int32_t* indptr, const int32_t* indices
                                    int64_t n_rows, int64_t n_cols, int64_t n_slices, int64_t slice_width, int32_t* segptr,
                                    int32_t* s_indices, int32_t* s_eid, void* workspace, size_t* workspace_bytes,
                                    hipStream_t s) {
-  const int slice_bits = bits_for(n_slices), row_bits = bits_for(n_rows);  // n_rows * n_slices < 2^31 (checked by the ABI)
+  const int slice_bits = bits_for(n_slices), row_bits = bits_for(n_rows);  // row_bits + slice_bits <= 31 (checked by the ABI)
   const size_t off_flag = 0;
   const size_t off_key_in = 256;
   const size_t off_key_out = off_key_in + align_up((size_t)E * 4, 256);

@@ -232,12 +232,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> csr_sliced_from_csr(const Tensor& ind
   TORCH_CHECK(indptr.numel() >= 1, "indptr is empty");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(indptr.device());
   const int64_t E = indices.numel(), n_rows = indptr.numel() - 1;
-  Tensor segptr = at::empty({n_slices * n_rows + 1}, indptr.options()), s_indices = at::empty({E}, indptr.options()),
-         s_eid = at::empty({E}, indptr.options());
-  size_t need = 0;
+  size_t need = 0;  // the size query first: a shape the ABI refuses is reported before anything is allocated for it
   check_status(dgmi_csr_sliced_from_csr_i32(nullptr, nullptr, nullptr, E, n_rows, n_cols, (int32_t)n_slices, nullptr, nullptr,
                                             nullptr, nullptr, &need, nullptr),
                "dgmi_csr_sliced_from_csr_i32(size query)");
+  Tensor segptr = at::empty({n_slices * n_rows + 1}, indptr.options()), s_indices = at::empty({E}, indptr.options()),
+         s_eid = at::empty({E}, indptr.options());
   Tensor ws = scratch(indptr, need < 256 ? 256 : need, kBuilder);
   size_t have = (size_t)ws.numel();
   check_status(dgmi_csr_sliced_from_csr_i32(indptr.data_ptr<int32_t>(), indices.data_ptr<int32_t>(), eid.data_ptr<int32_t>(), E,

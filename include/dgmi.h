@@ -219,7 +219,9 @@ DGMI_API int dgmi_csr_sliced_from_coo_i32(const int32_t* row, const int32_t* col
                                           dgmi_stream_t stream);
 /* The same layout from a CSR that dgmi_csr_from_coo_i32 built (indptr, indices, eid of E entries): one
  * stable partition pass by source slice instead of a full sort — the CSR is already in (row, input)
- * order.  Bit-identical output; same workspace protocol and error flag (an out-of-range source id). */
+ * order.  Bit-identical output; same workspace protocol and error flag (an out-of-range source id).
+ * DGMI_ERR_TOO_LARGE also when ceil(log2 n_rows) + ceil(log2 n_slices) (each at least 1) exceeds 31:
+ * the (slice, row) key of a position must fit the positive half of an int32. */
 DGMI_API int dgmi_csr_sliced_from_csr_i32(const int32_t* indptr, const int32_t* indices, const int32_t* eid,
                                           int64_t E, int64_t n_rows, int64_t n_cols, int32_t n_slices,
                                           int32_t* segptr, int32_t* sliced_indices, int32_t* sliced_eid,

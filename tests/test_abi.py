@@ -57,6 +57,13 @@ def test_argument_validation_returns_codes_without_a_gpu():
     assert L.dgmi_csr_from_coo_i32(None, None, -1, 4, 0, None, None, None, None, ctypes.byref(need), None) == -1
     assert L.dgmi_csr_from_coo_i32(None, None, 1, 4, 0, None, None, None, None, None, None) == -1
     assert L.dgmi_csr_from_coo_i32(None, None, 2 ** 31, 4, 0, None, None, None, None, ctypes.byref(need), None) == -2
+    # sliced from a CSR: the (slice << row_bits) | row key of a position must fit the positive half of an int32 — shapes whose
+    # row bits + slice bits exceed 31 are refused (size query included), their nearest neighbours are not
+    from_csr = lambda n_slices, n_rows: L.dgmi_csr_sliced_from_csr_i32(None, None, None, 10, n_rows, 5, n_slices, None, None, None,
+                                                                     None, ctypes.byref(need), None)
+    assert from_csr(33, 2 ** 25 + 1) == -2 and from_csr(5, 2 ** 28 + 1) == -2 and from_csr(3, 2 ** 29 + 1) == -2
+    assert from_csr(32, 2 ** 25 + 1) == 0 and from_csr(33, 2 ** 25) == 0 and need.value > 0
+    assert L.dgmi_csr_sliced_from_coo_i32(None, None, 10, 2 ** 25 + 1, 5, 33, None, None, None, None, ctypes.byref(need), None) == 0
     K0 = (None, None, 0)  # no edge dropout on the fly: eid, keep, n_keep
     E0 = (0, 0.0, None, 0, 1.0)  # no epilogue: act, act_slope, out_mask, ld_mask, out_mask_scale
     assert L.dgmi_spmm_csr_f32(None, None, None, *K0, None, 4, None, None, None, 4, -1, 1, 4, *E0, None) == -1

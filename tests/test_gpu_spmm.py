@@ -972,13 +972,14 @@ def test_compaction_invert_and_nested_descriptions_randomized(oracle, dev):
 
 
 @pytest.mark.parametrize("shape", [(300, 2500, 6000), (1, 5, 1), (40, 30, 0), (7, 9, 2047), (7, 9, 2048), (7, 9, 2049),
+                                   (7, 9, 4095), (7, 9, 4096), (7, 9, 4097),
                                    (2000, 100, 70000), (50, 4000, 131072), (3, 3, 64), (9000, 500, 40000)])
 @pytest.mark.parametrize("weighted", [False, True])
 def test_compacted_layout_is_the_layout_of_the_kept_edge_list(oracle, dev, shape, weighted):
     """(r4) `dgmi_compact_layout_i32`: the per-step replacement for the reference's graph rebuild (augmentation.py:48-65)
     at scale.  CSR and XCD-sliced layouts (8 and 3 slices) of the parent, compacted under plain, inverted and nested
     descriptions, are BIT-IDENTICAL to the same layouts built from the kept edge list — pointers, ids and values
-    (tile edges 2047 / 2048 / 2049, keep = 0, keep = E, empty rows, an empty graph)."""
+    (a tile is 4096 positions: 4095 / 4096 / 4097, and the half-tile sizes 2047 / 2048 / 2049; keep = 0, keep = E, empty rows, an empty graph)."""
     from dream_gnn_amd import _lib, ops
 
     n_dst, n_src, E = shape
