@@ -38,6 +38,7 @@ Tuning& tuning() {
     v.sliced_taper_rows = env_ll("DGMI_SLICED_TAPER_ROWS", 0);
     v.sliced_owned = (int)env_ll("DGMI_SLICED_OWNED", -1);
     v.sliced_owned_grid = (int)env_ll("DGMI_SLICED_OWNED_GRID", 0);
+    v.sliced_owned_wgs = (int)env_ll("DGMI_SLICED_OWNED_WGS", 0);
     v.sliced_owned_rows = (int)env_ll("DGMI_SLICED_OWNED_ROWS", 0);
     v.sliced_owned_lds_rows = env_ll("DGMI_SLICED_OWNED_LDS_ROWS", 0);
     v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
@@ -67,6 +68,7 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_taper_rows") == 0) t.sliced_taper_rows = value;
   else if (strcmp(name, "sliced_owned") == 0) t.sliced_owned = (int)value;
   else if (strcmp(name, "sliced_owned_grid") == 0) t.sliced_owned_grid = (int)value;
+  else if (strcmp(name, "sliced_owned_wgs") == 0) t.sliced_owned_wgs = (int)value;
   else if (strcmp(name, "sliced_owned_rows") == 0) t.sliced_owned_rows = (int)value;
   else if (strcmp(name, "sliced_owned_lds_rows") == 0) t.sliced_owned_lds_rows = value;
   else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;

@@ -23,8 +23,20 @@
 // should gather from the same slice at the same time, so a workgroup opens phase P for its workers once every workgroup
 // of its label has finished phase P - 1 - lag, or a time bound has passed.  Leaders wait, the slowest never does, every
 // spin is bounded and results never depend on it.  It is off unless asked for (kOwnedLag): measured, it costs more than it buys.
+// A launch without a gate carries no gate work: no memset of the arrive counters, no counting of a phase's tasks.
+//
+// Two forms of the one kernel (WAVES): a 16-wave workgroup per CU, or — the cap of 1024 threads per workgroup lifted —
+// two co-resident 12-wave workgroups per CU, each with half the LDS rows (owned_plan's wgs_per_cu): 22 workers instead
+// of 15, 6 waves per SIMD.  Their co-residency is asked of the runtime once per kernel and LDS size; where it says no,
+// the 16-wave form runs.  Nothing waits for the other workgroup of a CU.  Measured (profiles/owned_wgs/README.md): the
+// kernel is short of waves (12 instead of 16 per CU: +17-23 %), yet 512 free-running workgroups drift over more slices
+// than 256 and lose in L2 misses more than the waves return, so the built-in rule selects the second form for no class.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "dgmi_owned_common.h"
 #include "dgmi_sliced_common.h"
@@ -60,9 +72,11 @@ __device__ __forceinline__ OwnedWork owned_decode(const OwnedPlan& pl, int64_t w
   return w;
 }
 
-// VALS: 0 = unit edge values, 2 = multiplicities in the id words (dgmi_sliced.hip).
-template <int LPR, int VALS, bool OFF32>
-__global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
+// VALS: 0 = unit edge values, 2 = multiplicities in the id words (dgmi_sliced.hip).  WAVES: waves of the workgroup, the
+// last one the toucher: kOwnedWaves (one workgroup per CU, 4 waves per SIMD) or kOwnedPairWaves (two co-resident
+// workgroups per CU, 6 waves per SIMD: the register budget the second launch bound asks the compiler for).
+template <int LPR, int VALS, bool OFF32, int WAVES>
+__global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void spmm_owned_kernel(
     const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ X, int64_t ldx,
     const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy, int64_t n_dst, int F, OwnedPlan pl,
     unsigned* __restrict__ arrive, int lag, int64_t spin_ticks, Epilogue ep) {
@@ -76,17 +90,17 @@ __global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
   const int T = owned_wg_tasks(pl, wg);
   if (T == 0) return;  // block-uniform: a workgroup without rows
   int* done = reinterpret_cast<int*>(lds_rows + (size_t)pl.round_rows * LPR);  // [tasks] phases finished on a task slot
-  int* phase_cnt = done + pl.tasks;                                           // [phases] tasks finished of a phase
+  int* phase_cnt = done + pl.tasks;                                           // [phases] tasks finished of a phase (gate only)
   int* counter = phase_cnt + pl.phases;                                       // next task
   int* open = counter + 1;                                                    // highest phase the gate has opened
   for (int i = threadIdx.x; i < pl.tasks + pl.phases + 2; i += blockDim.x) done[i] = 0;
   __syncthreads();
   const int total = pl.phases * T;
   const int label = (int)(blockIdx.x & 7u);
-  const unsigned n_label = (unsigned)((pl.active - label + 7) >> 3);  // active workgroups with this label (>= 1: this one)
-  unsigned* my_arrive = arrive + (size_t)label * pl.phases;
 
-  if (wave == kOwnedWaves - 1) {  // ---- the toucher ----
+  if (wave == WAVES - 1) {  // ---- the toucher ----
+    const unsigned n_label = (unsigned)((pl.active - label + 7) >> 3);  // active workgroups with this label (>= 1: this one)
+    const unsigned* my_arrive = arrive + (size_t)label * pl.phases;
     // One loop does both jobs and blocks in neither: touch the next chunk of tasks once the counter is within the lead
     // of it (also across a phase boundary: while the workers stand at a closed gate the first tasks behind it get
     // touched), and open the next phase once its condition holds.
@@ -197,11 +211,15 @@ __global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
       t.y += acc.y;
       t.z += acc.z;
       t.w += acc.w;
-      if (w.slice < kOwnedSlices - 1) {
-        slot[r * LPR] = t;
-        return;
-      }
-      if (col_ok) {
+      slot[r * LPR] = t;
+    };
+    // The last slice's phase writes Y: dst_scale and the epilogue once per row, after the task's gathers — not inside
+    // commit, where the scale, the mask and the addresses of Y would be live next to 8 gathered rows — from the sums
+    // this lane has just left in LDS.
+    auto write_rows = [&]() {
+      if (w.slice != kOwnedSlices - 1 || !col_ok) return;
+      for (int r = 0; r < nr; ++r) {
+        float4 t = slot[r * LPR];
         const int64_t row = w.row0 + r;
         if (dst_scale != nullptr) {
           const float d = dst_scale[row];
@@ -229,24 +247,29 @@ __global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
         }
         for (int j = 0; j < n; j += kUnroll) {
           float4 v[kUnroll];
-          float m[kUnroll];
+          // the 8 multiplicity fields wait in one register while the rows are in flight: edge u's in bits 4u .. 4u + 2
+          static_assert(kUnroll == 8 && kMultShift == 28, "eight 4-bit fields, each shifted down from bit 28");
+          uint32_t mults = 0;
+          auto mult = [&](int u) { return (float)(((mults >> (4 * u)) & (uint32_t)kMultMax) + 1u); };
 #pragma unroll
           for (int u = 0; u < kUnroll; ++u) {
             int idx = __shfl(my_idx, gbase + j + u, kWave);
             if (MULT) {
-              m[u] = (float)(((idx >> kMultShift) & kMultMax) + 1);
+              mults = (mults >> 4) | ((uint32_t)idx & ((uint32_t)kMultMax << kMultShift));
               idx &= kIdMask;
             }
             v[u] = ld_row<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
           }
+          if (MULT) asm volatile("" : "+v"(mults));  // really one register: not the 8 id words kept for their fields
           if (base + j + kUnroll <= row_end) {  // all 8 edges belong to the current row
 #pragma unroll
             for (int u = 0; u < kUnroll; ++u) {
               if (MULT) {
-                acc.x = fmaf(m[u], v[u].x, acc.x);
-                acc.y = fmaf(m[u], v[u].y, acc.y);
-                acc.z = fmaf(m[u], v[u].z, acc.z);
-                acc.w = fmaf(m[u], v[u].w, acc.w);
+                const float m = mult(u);
+                acc.x = fmaf(m, v[u].x, acc.x);
+                acc.y = fmaf(m, v[u].y, acc.y);
+                acc.z = fmaf(m, v[u].z, acc.z);
+                acc.w = fmaf(m, v[u].w, acc.w);
               } else {
                 acc.x += v[u].x;
                 acc.y += v[u].y;
@@ -267,10 +290,11 @@ __global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
                 row_end = __shfl(my_b, gbase + r + 1, kWave);
               }
               if (MULT) {
-                acc.x = fmaf(m[u], v[u].x, acc.x);
-                acc.y = fmaf(m[u], v[u].y, acc.y);
-                acc.z = fmaf(m[u], v[u].z, acc.z);
-                acc.w = fmaf(m[u], v[u].w, acc.w);
+                const float m = mult(u);
+                acc.x = fmaf(m, v[u].x, acc.x);
+                acc.y = fmaf(m, v[u].y, acc.y);
+                acc.z = fmaf(m, v[u].z, acc.z);
+                acc.w = fmaf(m, v[u].w, acc.w);
               } else {
                 acc.x += v[u].x;
                 acc.y += v[u].y;
@@ -285,14 +309,18 @@ __global__ __launch_bounds__(kWave* kOwnedWaves) void spmm_owned_kernel(
         commit(r, acc);
         acc = make_float4(0.f, 0.f, 0.f, 0.f);
       }
+      write_rows();
     }
     // the next task's first ids, requested before this one is reported (its boundaries arrived long ago)
     nxt_idx = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows) : 0;
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
       __hip_atomic_store(&done[w.task], w.phase + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int finished = __hip_atomic_fetch_add(&phase_cnt[w.phase], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (finished == T - 1) __hip_atomic_fetch_add(&my_arrive[w.phase], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lag >= 0) {  // only a gate reads the arrive counters: without one nobody counts a phase's tasks either
+        const int finished = __hip_atomic_fetch_add(&phase_cnt[w.phase], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (finished == T - 1)
+          __hip_atomic_fetch_add(&arrive[(size_t)label * pl.phases + w.phase], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
     k = k_next;
     my_b = next_b;
@@ -314,25 +342,64 @@ int device_cus() {
 // run-to-run spread (profiles/owned_rows/README.md).  One class cleared that: a full-width table of 8 L2-sized slices
 // gathered into twice a workgroup's LDS rows (config 4's 50 000 sources -> 100 000 rows, unit values).  The two-pass
 // (half-width) products lose 5-9 % and the kNN-64 products are within their spread: they stay on the pair.
-bool owned_class_selected(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
-  return pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && table_bytes >= ((int64_t)16 << 20) && table_bytes <= ((int64_t)32 << 20);
+// `pl`: the plan of one workgroup per CU, which names the class.  0 = the pair, 1 = one 16-wave workgroup per CU,
+// 2 = two 12-wave workgroups per CU.  No class takes 2: forced for all 8 products of the step it ran every one of them
+// 30-35 % slower than the pair (profiles/owned_wgs/README.md); it stays behind sliced_owned_wgs = 2.
+int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+  if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && table_bytes >= ((int64_t)16 << 20) && table_bytes <= ((int64_t)32 << 20))
+    return 1;
+  return 0;
 }
 
-template <int LPR>
+// Whether `wgs` workgroups of `threads` threads and `lds` bytes of dynamic LDS of this kernel are resident on one CU
+// together, by the runtime's occupancy query; asked once per kernel and LDS size.  A speed question only: a grid that
+// does not co-reside runs in two rounds and is still correct, so the caller then takes the one-workgroup form.
+bool owned_coresident(const void* kern, int threads, size_t lds, int wgs) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, size_t>, int> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find({kern, lds});
+  if (it == known.end()) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      n = 0;
+    }
+    it = known.emplace(std::make_pair(kern, lds), n).first;
+  }
+  return it->second >= wgs;
+}
+
+// `resident` (the two-workgroup form only): false = its workgroups would not share a CU, nothing was launched.  The
+// 8-lane groups with multiplicities are not built in that form: they do not fit its 80 VGPRs without scratch.
+template <int LPR, int WAVES>
 hipError_t launch_owned(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, bool off32, int lag, int64_t spin_ticks,
-                        hipStream_t s) {
+                        hipStream_t s, bool* resident) {
+  constexpr int kWgsPerCu = WAVES == kOwnedWaves ? 1 : 2;
   unsigned* arrive = reinterpret_cast<unsigned*>(a.planes);
-  hipError_t err = hipMemsetAsync(arrive, 0, sizeof(unsigned) * 8 * (size_t)pl.phases, s);
-  if (err != hipSuccess) return err;
+  *resident = true;
 #define DGMI_OWNED(V, O)                                                                                                  \
   do {                                                                                                                    \
-    auto kern = spmm_owned_kernel<LPR, V, O>;                                                                             \
+    if constexpr (kWgsPerCu > 1 && LPR == 8 && V == 2) {                                                                  \
+      *resident = false;                                                                                                  \
+      return hipSuccess;                                                                                                  \
+    } else {                                                                                                              \
+    auto kern = spmm_owned_kernel<LPR, V, O, WAVES>;                                                                      \
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);            \
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (160 << 10) / kWgsPerCu); \
     if (attr != hipSuccess) return attr;                                                                                  \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave* kOwnedWaves), pl.lds_bytes, s, a.segptr, a.indices,        \
+    if (kWgsPerCu > 1 && !owned_coresident(reinterpret_cast<const void*>(kern), kWave * WAVES, pl.lds_bytes, kWgsPerCu)) { \
+      *resident = false;                                                                                                  \
+      return hipSuccess;                                                                                                  \
+    }                                                                                                                     \
+    if (lag >= 0) { /* only a gate reads the arrive counters */                                                           \
+      const hipError_t err = hipMemsetAsync(arrive, 0, sizeof(unsigned) * 8 * (size_t)pl.phases, s);                      \
+      if (err != hipSuccess) return err;                                                                                  \
+    }                                                                                                                     \
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave* WAVES), pl.lds_bytes, s, a.segptr, a.indices,              \
                        static_cast<const float*>(a.X), a.ldx, a.dst_scale, a.Y, a.ldy, a.n_dst, (int)a.F, pl, arrive, lag, \
                        spin_ticks, a.ep);                                                                                 \
+    }                                                                                                                     \
   } while (0)
   if (a.id_mult) {
     if (off32) DGMI_OWNED(2, true); else DGMI_OWNED(2, false);
@@ -352,25 +419,45 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   if (a.x_bytes != 4 || a.vals != nullptr || a.src_scale != nullptr || a.n_keep != 0 || a.n_slices != kOwnedSlices ||
       tune.sliced_chunk_rows > 0 || a.chunk_rows < a.n_dst || a.n_dst == 0 || a.F == 0)
     return hipSuccess;
+  // a forced grid counts workgroups, whichever form runs them
   const int64_t grid = tune.sliced_owned_grid > 0 ? tune.sliced_owned_grid : device_cus();
   if (grid < 1) return hipSuccess;
   const int lpr = sliced_lpr(a.F, a.n_src, a.n_slices, a.n_dst, a.full_width, a.n_keep, a.x_bytes, tune.sliced_lpr);
+  // the one-workgroup plan names the class and is what a two-workgroup launch that cannot co-reside falls back to
   const OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows);
   if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return hipSuccess;
   // the arrive counters live in the first bytes of the caller's plane workspace (n_slices * n_dst * ldp floats)
-  if (sizeof(unsigned) * 8 * (size_t)pl.phases > sizeof(float) * (size_t)a.n_slices * (size_t)a.n_dst * (size_t)a.ldp) return hipSuccess;
-  if (tune.sliced_owned != 1 &&
-      (a.n_dst < kOwnedMinRows || !owned_class_selected(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float))))
-    return hipSuccess;
+  const auto arrive_fits = [&](const OwnedPlan& p) {
+    return sizeof(unsigned) * 8 * (size_t)p.phases <= sizeof(float) * (size_t)a.n_slices * (size_t)a.n_dst * (size_t)a.ldp;
+  };
+  if (!arrive_fits(pl)) return hipSuccess;
+  const int rule = a.n_dst < kOwnedMinRows ? 0 : owned_class_form(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float));
+  if (tune.sliced_owned != 1 && rule == 0) return hipSuccess;
+  const int form = tune.sliced_owned_wgs == 1 || tune.sliced_owned_wgs == 2 ? tune.sliced_owned_wgs : (rule == 2 ? 2 : 1);
   const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * 4 < ((int64_t)1 << 32);
   const int64_t spin = tune.sliced_owned_spin_ticks > 0 ? tune.sliced_owned_spin_ticks : kOwnedSpinTicks;
   const int lag = tune.sliced_owned_lag >= -1 ? tune.sliced_owned_lag : kOwnedLag;
   *taken = true;
+  bool resident = true;
+  if (form == 2) {
+    const int64_t grid2 = tune.sliced_owned_grid > 0 ? grid : 2 * grid;
+    const OwnedPlan pl2 = owned_plan(a.n_dst, a.F, lpr, grid2, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 2);
+    if (pl2.ok && pl2.lds_bytes <= (size_t)(80 << 10) && arrive_fits(pl2)) {
+      hipError_t err;
+      switch (lpr) {
+        case 8: err = launch_owned<8, kOwnedPairWaves>(a, pl2, grid2, off32, lag, spin, s, &resident); break;
+        case 16: err = launch_owned<16, kOwnedPairWaves>(a, pl2, grid2, off32, lag, spin, s, &resident); break;
+        case 32: err = launch_owned<32, kOwnedPairWaves>(a, pl2, grid2, off32, lag, spin, s, &resident); break;
+        default: err = launch_owned<64, kOwnedPairWaves>(a, pl2, grid2, off32, lag, spin, s, &resident); break;
+      }
+      if (err != hipSuccess || resident) return err;
+    }
+  }
   switch (lpr) {
-    case 8: return launch_owned<8>(a, pl, grid, off32, lag, spin, s);
-    case 16: return launch_owned<16>(a, pl, grid, off32, lag, spin, s);
-    case 32: return launch_owned<32>(a, pl, grid, off32, lag, spin, s);
-    default: return launch_owned<64>(a, pl, grid, off32, lag, spin, s);
+    case 8: return launch_owned<8, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
+    case 16: return launch_owned<16, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
+    case 32: return launch_owned<32, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
+    default: return launch_owned<64, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
   }
 }
 

@@ -18,6 +18,7 @@ namespace dgmi {
 constexpr int kOwnedSlices = 8;                     // the form exists for 8 slices only (one per XCD)
 constexpr int kOwnedWaves = 16;                     // waves per workgroup: 15 workers and the toucher
 constexpr int kOwnedWorkers = kOwnedWaves - 1;
+constexpr int kOwnedPairWaves = 12;                 // the two-workgroups-per-CU form: 2 x (11 workers and a toucher)
 constexpr int64_t kOwnedLdsRowBytes = 144 << 10;    // LDS budget of the partial rows (the CU has 160 KiB)
 constexpr int kOwnedMaxPhases = 128;                // per-phase words live in LDS and in the arrive counters
 constexpr int kOwnedPhaseTasks = 24;                // built-in R aims at this many tasks per phase
@@ -49,18 +50,22 @@ struct OwnedTask {
 // wave (measured, profiles/owned_rows/README.md: fewer, longer tasks leave waves idle at the end of a phase, more and
 // shorter ones pay the start of a task — boundaries, then ids, then the first gathers — too often; a task still
 // practically never waits for its predecessor of the phase before); `lds_rows_cap` > 0: at most that many LDS rows
-// (forces row rounds).
-__host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap) {
+// (forces row rounds); `wgs_per_cu`: 1 = one 16-wave workgroup per CU, 2 = two co-resident 12-wave workgroups, each with
+// half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way).
+__host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
+
+__host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap,
+                                                int wgs_per_cu = 1) {
   OwnedPlan p{};
   p.ok = false;
   p.n_dst = n_dst;
-  if (n_dst < 1 || F < 1 || grid < 1 || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64)) return p;
+  if (n_dst < 1 || F < 1 || grid < 1 || (wgs_per_cu != 1 && wgs_per_cu != 2) || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64)) return p;
   p.lpr = lpr;
   p.G = 64 / lpr;
   p.col_rounds = (int)((F + 4 * lpr - 1) / (4 * lpr));
   p.wg_rows = (n_dst + grid - 1) / grid;
   p.active = (n_dst + p.wg_rows - 1) / p.wg_rows;
-  int64_t fit = kOwnedLdsRowBytes / (16 * lpr);
+  int64_t fit = kOwnedLdsRowBytes / wgs_per_cu / (16 * lpr);
   if (lds_rows_cap > 0 && lds_rows_cap < fit) fit = lds_rows_cap;
   const int64_t rounds = (p.wg_rows + fit - 1) / fit;
   if (rounds * p.col_rounds * kOwnedSlices > kOwnedMaxPhases) return p;
@@ -69,7 +74,9 @@ __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lp
   p.phases = p.col_rounds * p.row_rounds * kOwnedSlices;
   int R = R_req;
   if (R <= 0) {
-    R = (p.round_rows + kOwnedPhaseTasks * p.G / 2) / (kOwnedPhaseTasks * p.G);  // rounded to nearest
+    // 1.6 tasks per worker wave: 24 for 15 workers, 18 for 11
+    const int phase_tasks = (kOwnedPhaseTasks * (owned_form_waves(wgs_per_cu) - 1) + kOwnedWorkers / 2) / kOwnedWorkers;
+    R = (p.round_rows + phase_tasks * p.G / 2) / (phase_tasks * p.G);  // rounded to nearest
     if (R > kOwnedMaxRows) R = kOwnedMaxRows;
   }
   if (R > lpr - 1) R = lpr - 1;  // a group's row boundaries live one per lane

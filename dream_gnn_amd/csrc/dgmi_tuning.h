@@ -15,7 +15,8 @@ struct Tuning {
   int64_t sliced_taper_rows = 0;    // DGMI_SLICED_TAPER_ROWS: last rows of a chunk in shorter runs (-1: off, 0: built-in)
   int sliced_owned = -1;            // DGMI_SLICED_OWNED: the workgroup-owned form (dgmi_owned.hip) 0 = never, 1 = whenever applicable, -1 = built-in rule
   int sliced_owned_grid = 0;        // DGMI_SLICED_OWNED_GRID: its workgroups (0: one per CU)
-  int sliced_owned_rows = 0;        // DGMI_SLICED_OWNED_ROWS: rows per lane group and task (0: built-in)
+  int sliced_owned_wgs = 0;         // DGMI_SLICED_OWNED_WGS: its workgroups per CU (0: built-in, 1: one of 16 waves, 2: two of 12 waves)
+  int sliced_owned_rows = 0;       // DGMI_SLICED_OWNED_ROWS: rows per lane group and task (0: built-in)
   int64_t sliced_owned_lds_rows = 0;  // DGMI_SLICED_OWNED_LDS_ROWS: cap on a workgroup's LDS rows (forces row rounds; 0: the LDS budget)
   int sliced_owned_lag = -2;        // DGMI_SLICED_OWNED_LAG: phases a workgroup may run ahead of its XCD's slowest (-1: no gate, -2: built-in)
   int64_t sliced_owned_spin_ticks = 0;  // DGMI_SLICED_OWNED_SPIN_TICKS: bound of one gate wait, 100 MHz ticks (0: built-in)
