@@ -17,6 +17,15 @@
 // a reserved task is only ever held by a wave that runs an earlier one), so this cannot deadlock; it also orders the
 // reuse of the LDS rows by the next round.
 //
+// A worker keeps a ROLLING WINDOW of gathers in flight across its lane groups' whole runs (all R rows of the task):
+// right after it has added edge e's row to the sum it issues edge e + W into the registers that row has left, so the
+// gathers in flight stay at W from the first group of a run to its last instead of swinging between W and 0 once per
+// batch — at 4 waves per SIMD nobody else fills that hole.  The sum still takes the edges one at a time, in order.  The
+// window's index arithmetic (id batches of W, the clamp past the end of a run): owned_window, dgmi_owned_common.h.  It
+// drains at the end of a task.  Measured (profiles/owned_window/README.md): W = 4 — no more rows in flight than the
+// batches of 8 averaged, but never none; at W = 8 the unit-value products lose 4-8 points of L2 hits — runs the kNN-64
+// classes 20 % and 9 % and the unit-value classes 6 % faster in loops of their own, the step of bench.py 5 %.
+//
 // The 16th wave is the toucher: it walks the same task order a few tasks ahead of the counter and touches one word per
 // 128-B line of the boundaries and ids the workers are about to read (they issue no cold loads), and it keeps the
 // ADVISORY phase gate: the workgroups of an XCD (label blockIdx % 8 — a speed assumption, as is their co-residency)
@@ -173,17 +182,19 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
     if (w.rows == 0) return 0;
     return segptr[(int64_t)w.slice * n_dst + w.row0 + (glane < w.rows ? glane : w.rows)];
   };
-  // the first id batch of a group whose boundaries have arrived
-  auto first_ids = [&](int my_b, int rows) {
+  // id batch `batch` (0 / 1: the two a run starts with, owned_window) of a group whose boundaries have arrived
+  auto first_ids = [&](int my_b, int rows, int batch) {
     const int e_begin = __shfl(my_b, gbase, kWave), e_end = __shfl(my_b, gbase + rows, kWave);
     if (rows == 0 || e_begin >= e_end) return 0;
-    return indices[e_begin + glane < e_end ? e_begin + glane : e_begin];
+    return indices[e_begin + owned_window_id_edge(batch, glane, e_end - e_begin)];
   };
+  static_assert(kOwnedWindowFirstBatches == 2, "nxt_idx and nxt_idx1");
 
   const uint32_t row_bytes = (uint32_t)ldx * 4u;
   int k = grab();
   int my_b = boundaries(k);
-  int nxt_idx = k < total ? first_ids(my_b, owned_decode(pl, wg, T, k, grp).rows) : 0;
+  int nxt_idx = k < total ? first_ids(my_b, owned_decode(pl, wg, T, k, grp).rows, 0) : 0;
+  int nxt_idx1 = k < total ? first_ids(my_b, owned_decode(pl, wg, T, k, grp).rows, 1) : 0;
   while (k < total) {
     const OwnedWork w = owned_decode(pl, wg, T, k, grp);
     const int k_next = grab();
@@ -238,70 +249,80 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
       int r = 0;
       int row_end = __shfl(my_b, gbase + 1, kWave);
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int base = e_begin; base < e_end; base += LPR) {
-        const int n = min(LPR, e_end - base);
-        const int my_idx = nxt_idx;
-        if (base + LPR < e_end) {
-          const int nb = base + LPR;
-          nxt_idx = indices[nb + glane < e_end ? nb + glane : nb];
-        }
-        for (int j = 0; j < n; j += kUnroll) {
-          float4 v[kUnroll];
-          // the 8 multiplicity fields wait in one register while the rows are in flight: edge u's in bits 4u .. 4u + 2
-          static_assert(kUnroll == 8 && kMultShift == 28, "eight 4-bit fields, each shifted down from bit 28");
-          uint32_t mults = 0;
-          auto mult = [&](int u) { return (float)(((mults >> (4 * u)) & (uint32_t)kMultMax) + 1u); };
+      if (e_begin < e_end) {
+        // The rolling window (owned_window, dgmi_owned_common.h): W rows in flight from the prologue to the last group;
+        // the sum takes the edges in order, one at a time, exactly as the pair's gather does.
+        constexpr int W = kOwnedWindow;
+        static_assert(W <= 8 && kMultShift == 28 && LPR % W == 0, "at most eight 4-bit multiplicity fields, shifted down from bit 28");
+        const int L = e_end - e_begin;
+        float4 v[W];
+        int idx[W];  // the ids of a group's W issues, read at its top: an issue is a multiply and a load
+        // The multiplicity fields of the W rows in flight wait in one register, the next edge's in bits 32 - 4 W ..: a
+        // consumed field is shifted out, a new one comes in at bit 28.  Those of the W ids read at a group's top collect
+        // in a second register and replace the first after the group.
+        uint32_t mults = 0, mults_in = 0;
+        auto read_ids = [&](int batch_idx) {  // lanes 0 .. W - 1 of the group's id batch
 #pragma unroll
-          for (int u = 0; u < kUnroll; ++u) {
-            int idx = __shfl(my_idx, gbase + j + u, kWave);
+          for (int u = 0; u < W; ++u) {
+            int id = __shfl(batch_idx, gbase + u, kWave);
             if (MULT) {
-              mults = (mults >> 4) | ((uint32_t)idx & ((uint32_t)kMultMax << kMultShift));
-              idx &= kIdMask;
+              mults_in = (mults_in >> 4) | ((uint32_t)id & ((uint32_t)kMultMax << kMultShift));
+              id &= kIdMask;
             }
-            v[u] = ld_row<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
+            idx[u] = id;
           }
-          if (MULT) asm volatile("" : "+v"(mults));  // really one register: not the 8 id words kept for their fields
-          if (base + j + kUnroll <= row_end) {  // all 8 edges belong to the current row
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-              if (MULT) {
-                const float m = mult(u);
-                acc.x = fmaf(m, v[u].x, acc.x);
-                acc.y = fmaf(m, v[u].y, acc.y);
-                acc.z = fmaf(m, v[u].z, acc.z);
-                acc.w = fmaf(m, v[u].w, acc.w);
-              } else {
-                acc.x += v[u].x;
-                acc.y += v[u].y;
-                acc.z += v[u].z;
-                acc.w += v[u].w;
-              }
-            }
-            continue;
+          if (MULT) asm volatile("" : "+v"(mults_in));  // really one register: not the W id words kept for their fields
+        };
+        auto add = [&](int u) {  // acc + x / fmaf(m, x, acc): the canonical step
+          if (MULT) {
+            const float m = (float)(((mults >> (32 - 4 * W)) & (uint32_t)kMultMax) + 1u);
+            mults >>= 4;
+            acc.x = fmaf(m, v[u].x, acc.x);
+            acc.y = fmaf(m, v[u].y, acc.y);
+            acc.z = fmaf(m, v[u].z, acc.z);
+            acc.w = fmaf(m, v[u].w, acc.w);
+          } else {
+            acc.x += v[u].x;
+            acc.y += v[u].y;
+            acc.z += v[u].z;
+            acc.w += v[u].w;
           }
+        };
+        auto rows_before = [&](int p) {  // row(s) ended before edge p (empty rows commit zeros)
+          while (p >= row_end) {
+            commit(r, acc);
+            acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            ++r;
+            row_end = __shfl(my_b, gbase + r + 1, kWave);
+          }
+        };
+        read_ids(nxt_idx);
+        int ids = nxt_idx1;  // the id batch of the next issues
 #pragma unroll
-          for (int u = 0; u < kUnroll; ++u) {
-            const int p = base + j + u;
-            if (p < e_end) {  // group-uniform
-              while (p >= row_end) {  // row(s) ended before this edge (empty rows commit zeros)
-                commit(r, acc);
-                acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                ++r;
-                row_end = __shfl(my_b, gbase + r + 1, kWave);
-              }
-              if (MULT) {
-                const float m = mult(u);
-                acc.x = fmaf(m, v[u].x, acc.x);
-                acc.y = fmaf(m, v[u].y, acc.y);
-                acc.z = fmaf(m, v[u].z, acc.z);
-                acc.w = fmaf(m, v[u].w, acc.w);
-              } else {
-                acc.x += v[u].x;
-                acc.y += v[u].y;
-                acc.z += v[u].z;
-                acc.w += v[u].w;
-              }
-            }
+        for (int u = 0; u < W; ++u) v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+        mults = mults_in;
+        // The scheduling barriers pin every gather right behind the consumption of the row it replaces: left alone, the
+        // scheduler sinks each load down to its use and two are in flight instead of W.
+        __builtin_amdgcn_sched_barrier(0);
+        int p0 = e_begin;
+        for (int g = 0; p0 + W < e_end; ++g, p0 += W) {  // group g: W edges of the run, and something to issue
+          read_ids(ids);  // batch g + 1, requested W gathers ago or more
+          ids = indices[e_begin + owned_window_id_edge(owned_window_request_batch(g), glane, L)];  // unconditional: clamped
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int u = 0; u < W; ++u) {
+            rows_before(p0 + u);
+            add(u);
+            v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          mults = mults_in;
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {  // the last group: 1 .. W edges, nothing left to issue — the window drains
+          if (p0 + u < e_end) {        // group-uniform
+            rows_before(p0 + u);
+            add(u);
           }
         }
       }
@@ -312,7 +333,8 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
       write_rows();
     }
     // the next task's first ids, requested before this one is reported (its boundaries arrived long ago)
-    nxt_idx = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows) : 0;
+    nxt_idx = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows, 0) : 0;
+    nxt_idx1 = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows, 1) : 0;
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
       __hip_atomic_store(&done[w.task], w.phase + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -339,15 +361,21 @@ int device_cus() {
 
 // The built-in rule: the classes (column rounds, row rounds, multiplicities in the ids, bytes of the source table) whose
 // product, inside the step of bench.py, was faster with this form than with the pair by more than the pair's own
-// run-to-run spread (profiles/owned_rows/README.md).  One class cleared that: a full-width table of 8 L2-sized slices
-// gathered into twice a workgroup's LDS rows (config 4's 50 000 sources -> 100 000 rows, unit values).  The two-pass
-// (half-width) products lose 5-9 % and the kNN-64 products are within their spread: they stay on the pair.
+// run-to-run spread.  Three classes cleared that:
+//  - a full-width table of 8 L2-sized slices gathered into twice a workgroup's LDS rows (config 4's 50 000 sources ->
+//    100 000 rows, unit values): profiles/owned_rows/README.md;
+//  - with the rolling gather window (profiles/owned_window/README.md) both kNN-64 classes: the half-width 100 000-node
+//    one (two column rounds, one row round, 51 MB table: -10 %) and the full-width 50 000-node one (one column round, one
+//    row round: -7 %).
+// The two-pass unit-value products (100 000 sources -> 50 000 rows) are within a spread of the pair: they stay on it.
 // `pl`: the plan of one workgroup per CU, which names the class.  0 = the pair, 1 = one 16-wave workgroup per CU,
 // 2 = two 12-wave workgroups per CU.  No class takes 2: forced for all 8 products of the step it ran every one of them
 // 30-35 % slower than the pair (profiles/owned_wgs/README.md); it stays behind sliced_owned_wgs = 2.
 int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
-  if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && table_bytes >= ((int64_t)16 << 20) && table_bytes <= ((int64_t)32 << 20))
-    return 1;
+  const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return 1;
+  if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return 1;
+  if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return 1;
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // dgmi_owned_common.h — the plan of the workgroup-owned form of the XCD-local SpMM (dgmi_owned.hip): which destination
 // rows a workgroup owns, how they are cut into rounds that fit its LDS, and which rows a task of a phase sums.  The
 // kernel, its launcher and the host test (tests/test_owned_plan_host.py) use owned_plan / owned_phase / owned_task and
-// nothing else.
+// nothing else.  At the end: the index arithmetic of the kernel's rolling gather window (owned_window_*).
 //
 // Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
 // column tile (16 LPR bytes) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
@@ -119,6 +119,34 @@ __host__ __device__ inline OwnedTask owned_task(const OwnedPlan& p, int64_t wg, 
   int64_t rows = owned_round_rows(p, wg, row_round) - lds_row;
   rows = rows < 0 ? 0 : (rows < p.R ? rows : p.R);
   return OwnedTask{wg * p.wg_rows + (int64_t)row_round * p.round_rows + lds_row, (int)lds_row, (int)rows};
+}
+
+// The rolling gather window.  A lane group sums the L edges of its run (all the rows of its task, in order) with
+// W = kOwnedWindow gathers in flight: a prologue issues edges 0 .. W - 1; GROUP g then consumes edges g W .. g W + W - 1
+// in order and, right after consuming edge e, issues edge e + W into the registers e's row has just left — except in the
+// last group (owned_window_groups(L) - 1), which only consumes.  The ids arrive in BATCHES of W, whatever the lane-group
+// width: one register, in which lane l of the group holds the id of edge b W + l % W of batch b, clamped to the run's
+// last edge — so an edge issued past the end of the run gathers the run's last row again (an L1 hit, never one fixed
+// row) and is never consumed.  Batches 0 and 1 are requested before the run starts (during the task before).  At its
+// top group g reads the W ids of its issues (batch g + 1) out of the register and then requests batch g + 2 into it:
+// a batch is read W gathers after it was requested, so, vmcnt being in order, waiting for it waits for nothing but
+// gathers already consumed, and the request itself never waits.
+// The kernel and the host test (tests/test_owned_window_host.py) take all of this from the functions below.
+// The depth is measured (profiles/owned_window/README.md): inside the step of bench.py a window of 4 beats one of 8 on
+// every class (8 in flight per lane group cost the unit-value products 4-8 points of L2 hits) and one of 2 loses 15 %.
+constexpr int kOwnedWindow = 4;              // gathers in flight per lane group; divides every lane-group width
+constexpr int kOwnedWindowFirstBatches = 2;  // id batches requested before a run starts
+
+__host__ __device__ constexpr int owned_window_groups(int L) { return (L + kOwnedWindow - 1) / kOwnedWindow; }
+
+// Group `g` (not the last one of its run) issues edges (g + 1) W + u, u = 0 .. W - 1, from lanes u of this id batch ...
+__host__ __device__ constexpr int owned_window_issue_batch(int g) { return g + 1; }
+// ... and requests this one at its top.
+__host__ __device__ constexpr int owned_window_request_batch(int g) { return g + kOwnedWindowFirstBatches; }
+
+// The edge (0-based in its run of L > 0 edges) whose id lane `lane` of a lane group loads for id batch `batch`: the clamp.
+__host__ __device__ constexpr int owned_window_id_edge(int batch, int lane, int L) {
+  return batch * kOwnedWindow + lane % kOwnedWindow < L ? batch * kOwnedWindow + lane % kOwnedWindow : L - 1;
 }
 
 }  // namespace dgmi
