@@ -75,6 +75,9 @@ __global__ __launch_bounds__(kBlock) void gather_concat_dword_kernel(
   }
 }
 
+// relu as the reference's torch.relu computes it: a NaN sum stays NaN (fmaxf(x, 0) would return 0 for it), -inf -> 0
+__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.f ? 0.f : x; }
+
 // out[e] = A[src[e]] + B[dst[e]] (+ bias): VEC = 4 (16-B path) or 1; thread t handles element
 // group (t % W) of edge (t / W), W = F / VEC, grid-strided.
 template <int VEC, bool HAS_BIAS>
@@ -105,16 +108,16 @@ __global__ __launch_bounds__(kBlock) void gather_add_kernel(
         x.w += z.w;
       }
       if (act == 1) {  // relu in the pass that writes the E x F result (the decoder's next op, layers.py:366)
-        x.x = fmaxf(x.x, 0.f);
-        x.y = fmaxf(x.y, 0.f);
-        x.z = fmaxf(x.z, 0.f);
-        x.w = fmaxf(x.w, 0.f);
+        x.x = relu_keep_nan(x.x);
+        x.y = relu_keep_nan(x.y);
+        x.z = relu_keep_nan(x.z);
+        x.w = relu_keep_nan(x.w);
       }
       *reinterpret_cast<float4*>(o) = x;
     } else {
       float x = a[0] + b[0];
       if (HAS_BIAS) x += bias[c];
-      if (act == 1) x = fmaxf(x, 0.f);
+      if (act == 1) x = relu_keep_nan(x);
       o[0] = x;
     }
   }

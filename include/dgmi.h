@@ -259,6 +259,7 @@ DGMI_API int dgmi_gather_concat_f32(const int32_t* src, const int32_t* dst, int6
  * matrix and the E x 2F x H GEMM altogether.  Same bytes-per-edge shape as the gather-concat:
  * bound by the streaming write of E*4*F bytes.  bias may be NULL.  act = 1: out = relu(...) — the
  * decoder's next operation (layers.py:366) in the pass that writes the E x F result; 0: none.
+ * The relu is torch.relu's: a NaN sum stays NaN, -inf becomes 0, +inf stays.
  */
 DGMI_API int dgmi_gather_add_f32(const int32_t* src, const int32_t* dst, int64_t E, const float* A,
                                  int64_t lda, const float* B, int64_t ldb, const float* bias,

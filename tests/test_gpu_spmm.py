@@ -527,7 +527,7 @@ def test_gather_add_forward_backward(oracle, dev, F):
                                     (3_000_000, 2_700_000), (3_000_000, 3_000_000), (3_000_000, 0), (10_000_000, 9_000_000)])
 def test_random_subset_mask_bit_exact(oracle, dev, E, keep):
     """(D3) exact-size random edge selection: integer work, bit-exact against the oracle.  Lists below
-    2^20 edges are selected by one workgroup (radix select), longer ones by the uniform-window passes
+    2^16 edges are selected by one workgroup (radix select), longer ones by the uniform-window passes
     (keep = 1 / E - 1 at the window's edge of the hash space; keep = E and 0: the direct paths)."""
     from dream_gnn_amd import ops
 
