@@ -41,6 +41,7 @@ Tuning& tuning() {
     v.sliced_owned_wgs = (int)env_ll("DGMI_SLICED_OWNED_WGS", 0);
     v.sliced_owned_rows = (int)env_ll("DGMI_SLICED_OWNED_ROWS", 0);
     v.sliced_owned_lds_rows = env_ll("DGMI_SLICED_OWNED_LDS_ROWS", 0);
+    v.sliced_owned_workers = (int)env_ll("DGMI_SLICED_OWNED_WORKERS", 0);
     v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
     v.sliced_owned_spin_ticks = env_ll("DGMI_SLICED_OWNED_SPIN_TICKS", 0);
     v.select_window_min = env_ll("DGMI_SELECT_WINDOW_MIN", 0);
@@ -71,6 +72,7 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_owned_wgs") == 0) t.sliced_owned_wgs = (int)value;
   else if (strcmp(name, "sliced_owned_rows") == 0) t.sliced_owned_rows = (int)value;
   else if (strcmp(name, "sliced_owned_lds_rows") == 0) t.sliced_owned_lds_rows = value;
+  else if (strcmp(name, "sliced_owned_workers") == 0) t.sliced_owned_workers = (int)value;
   else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;
   else if (strcmp(name, "sliced_owned_spin_ticks") == 0) t.sliced_owned_spin_ticks = value;
   else if (strcmp(name, "select_window_min") == 0) t.select_window_min = value;

@@ -21,10 +21,21 @@
 // right after it has added edge e's row to the sum it issues edge e + W into the registers that row has left, so the
 // gathers in flight stay at W from the first group of a run to its last instead of swinging between W and 0 once per
 // batch — at 4 waves per SIMD nobody else fills that hole.  The sum still takes the edges one at a time, in order.  The
-// window's index arithmetic (id batches of W, the clamp past the end of a run): owned_window, dgmi_owned_common.h.  It
-// drains at the end of a task.  Measured (profiles/owned_window/README.md): W = 4 — no more rows in flight than the
-// batches of 8 averaged, but never none; at W = 8 the unit-value products lose 4-8 points of L2 hits — runs the kNN-64
-// classes 20 % and 9 % and the unit-value classes 6 % faster in loops of their own, the step of bench.py 5 %.
+// window's index arithmetic (id batches of W, the clamp past the end of a run): owned_window, dgmi_owned_common.h.
+// Measured (profiles/owned_window/README.md): W = 4 — no more rows in flight than the batches of 8 averaged, but never
+// none; at W = 8 the unit-value products lose 4-8 points of L2 hits — runs the kNN-64 classes 20 % and 9 % and the
+// unit-value classes 6 % faster in loops of their own, the step of bench.py 5 %.
+//
+// The window is HANDED OVER from task to task (owned_carry, dgmi_owned_common.h; the 16-wave form with multiplicities
+// in the ids — the other instantiations keep the draining loop, see CARRY): in the last group of
+// its run a lane group refills every slot, right behind its consumption, with the first W edges of its run in the
+// wave's next task — that task's ids, its column offset — so the next task starts with its window full: no prologue,
+// no wait for ids.  The next task's boundaries are requested when it is reserved and taken over at ONE wave-uniform
+// point per task, behind the wait for done[]: there its run is found, its first two id batches and its scales are
+// requested, and the wait for the boundaries is the wait for the carried gathers the first group needs at once.  A run
+// behind a run without edges starts cold, as does a wave's first; a run in front of one without edges hands nothing over,
+// and past the last task nothing is issued.  A task is decoded once, when it is reserved.  The sums, their order and every bit stay what they were.  Measured:
+// profiles/owned_carry/README.md.
 //
 // The 16th wave is the toucher: it walks the same task order a few tasks ahead of the counter and touches one word per
 // 128-B line of the boundaries and ids the workers are about to read (they issue no cold loads), and it keeps the
@@ -61,21 +72,28 @@ constexpr int64_t kOwnedMinRows = 32768;   // built-in rule: below, a workgroup 
 // 35-45 % and lag 1 25-30 % of a product, far more than the L2 hits it buys (profiles/owned_rows/README.md).
 constexpr int kOwnedLag = -1;
 
-struct OwnedWork {  // task k of a workgroup, decoded (wave-uniform except row0 / lds_row / rows: per lane group)
+struct OwnedWork {  // task k of a workgroup, decoded (wave-uniform except lds_row / rows: per lane group)
   int phase, task, slice, col_round;
-  int64_t row0;
+  int64_t row_base;  // the lane group's first destination row is row_base + lds_row
   int lds_row, rows;
 };
 
+// Decoded once, when a wave reserves the task, and carried.  `k` past the last task: a task without rows.
 __device__ __forceinline__ OwnedWork owned_decode(const OwnedPlan& pl, int64_t wg, int T, int k, int grp) {
   OwnedWork w;
+  if (k >= pl.phases * T) {  // wave-uniform
+    w.phase = pl.phases;
+    w.task = w.slice = w.col_round = w.lds_row = w.rows = 0;
+    w.row_base = 0;
+    return w;
+  }
   w.phase = k / T;
   w.task = k - w.phase * T;
   const OwnedPhase ph = owned_phase(pl, w.phase);
   w.slice = ph.slice;
   w.col_round = ph.col_round;
   const OwnedTask t = owned_task(pl, wg, ph.row_round, w.task, grp);
-  w.row0 = t.row0;
+  w.row_base = t.row0 - t.lds_row;
   w.lds_row = t.lds_row;
   w.rows = t.rows;
   return w;
@@ -88,9 +106,14 @@ template <int LPR, int VALS, bool OFF32, int WAVES>
 __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void spmm_owned_kernel(
     const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ X, int64_t ldx,
     const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy, int64_t n_dst, int F, OwnedPlan pl,
-    unsigned* __restrict__ arrive, int lag, int64_t spin_ticks, Epilogue ep) {
+    unsigned* __restrict__ arrive, int lag, int64_t spin_ticks, int workers, Epilogue ep) {
   constexpr bool MULT = VALS == 2;
   constexpr int kIdMask = MULT ? (int)kMultIdMask : 0x7fffffff;
+  // The window is handed from task to task (false: every run starts cold — the same bits).  Not in the two-workgroup
+  // form: next to its 80 VGPRs the window and the next task's run do not stay in registers across the boundary.  Not
+  // for unit values either: measured (profiles/owned_carry/README.md), their products lose 2 points of L2 hits and
+  // 0.3-0.6 % of their time to it, while the products with multiplicities gain.
+  constexpr bool CARRY = WAVES == kOwnedWaves && MULT;
   extern __shared__ float4 lds_rows[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
@@ -170,46 +193,106 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
   }
 
   // ---- the workers ----
+  if (workers > 0 && wave >= workers) return;  // (sliced_owned_workers: the first `workers` of them run every task)
   auto grab = [&]() {
     int k = 0;
     if (lane == 0) k = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     return __builtin_amdgcn_readfirstlane(k);
   };
-  // lane j of a group holds boundary j of the group's rows (j <= rows)
-  auto boundaries = [&](int k) {
-    if (k >= total) return 0;
-    const OwnedWork w = owned_decode(pl, wg, T, k, grp);
-    if (w.rows == 0) return 0;
-    return segptr[(int64_t)w.slice * n_dst + w.row0 + (glane < w.rows ? glane : w.rows)];
+  // lane j of a group holds boundary j of the group's rows (j <= rows); a task without rows reads segptr[0] into every
+  // lane: an empty run as well
+  auto boundaries = [&](const OwnedWork& t) {
+    return segptr[t.rows == 0 ? 0 : (int64_t)t.slice * n_dst + t.row_base + (t.lds_row + (glane < t.rows ? glane : t.rows))];
   };
-  // id batch `batch` (0 / 1: the two a run starts with, owned_window) of a group whose boundaries have arrived
-  auto first_ids = [&](int my_b, int rows, int batch) {
-    const int e_begin = __shfl(my_b, gbase, kWave), e_end = __shfl(my_b, gbase + rows, kWave);
-    if (rows == 0 || e_begin >= e_end) return 0;
-    return indices[e_begin + owned_window_id_edge(batch, glane, e_end - e_begin)];
+  // lane j of a group holds dst_scale of the group's row j: only the last slice's phase, which writes Y, asks for it
+  auto scales = [&](const OwnedWork& t) {
+    if (!CARRY || dst_scale == nullptr || t.slice != kOwnedSlices - 1 || t.rows == 0) return 0.f;
+    return dst_scale[t.row_base + (t.lds_row + (glane < t.rows ? glane : t.rows - 1))];
   };
+  // The hand-over point of a task, WAVE-UNIFORM and right behind the wait for done[]: the boundaries `b` of the NEXT
+  // task, requested when it was reserved, are waited for — with them (vmcnt is in order) the gathers the task before
+  // has carried into this one, which this task's first group consumes at once; nothing else is in flight.  It finds
+  // the group's run [beg, end) in the next task, keeps its boundaries relative to beg, requests the two id batches a
+  // run starts with (owned_window; nothing is read for a run without edges) and the scales of the next task's rows;
+  // those requested at the task before are this task's (my_ds): write_rows waits for no load.  Why here and not a
+  // group later, without any wait: the lane groups of a wave diverge, and the compiler counts the loads in flight
+  // along every path through the linearised branches — also those on which a group has issued nothing; a load
+  // consumed inside a branch is, for it, still pending after the branch, and the next wait for it (or for the
+  // registers it has left) empties the window.  At a uniform point every count is exact
+  // (profiles/owned_carry/README.md).
+  int nxt_idx = 0, nxt_idx1 = 0, rel_b = 0;
+  float my_ds = 0.f, nxt_ds = 0.f;
   static_assert(kOwnedWindowFirstBatches == 2, "nxt_idx and nxt_idx1");
+  auto hand_over = [&](int b, const OwnedWork& nxt, int& beg, int& end) {
+    beg = __shfl(b, gbase, kWave);
+    rel_b = b - beg;
+    end = beg + __shfl(rel_b, gbase + nxt.rows, kWave);
+    if (beg < end) {  // lane l of batch 0 holds the id slot l % W is refilled with, or the prologue issues
+      nxt_idx = indices[beg + owned_carry_slot_edge(glane % kOwnedWindow, end - beg)];
+      nxt_idx1 = indices[beg + owned_window_id_edge(owned_carry_start_batch(), glane, end - beg)];
+    }
+    my_ds = nxt_ds;
+    nxt_ds = scales(nxt);
+  };
+
+  // The window (owned_window, owned_carry: dgmi_owned_common.h) lives across the tasks of a wave.
+  constexpr int W = kOwnedWindow;
+  static_assert(W <= 8 && kMultShift == 28 && LPR % W == 0, "at most eight 4-bit multiplicity fields, shifted down from bit 28");
+  float4 v[W];
+  int idx[W];   // the ids of a group's W issues, read at its top: an issue is a multiply and a load
+  int nidx[W];  // the ids of the W edges the last group of a run carries into the next task
+  // The multiplicity fields of the W rows in flight wait in one register, the next edge's in bits 32 - 4 W ..: a
+  // consumed field is shifted out, a new one comes in at bit 28.  Those of the W ids read at a group's top collect
+  // in a second register and replace the first after the group.
+  uint32_t mults = 0, mults_in = 0, nmults = 0;
+  bool carried = false;  // per lane group: its window is full of the first W edges of the run it is about to sum
+  auto read_batch = [&](int batch_idx, int (&out)[W], uint32_t& fields) {  // lanes 0 .. W - 1 of the group's id batch
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+      int id = __shfl(batch_idx, gbase + u, kWave);
+      if (MULT) {
+        fields = (fields >> 4) | ((uint32_t)id & ((uint32_t)kMultMax << kMultShift));
+        id &= kIdMask;
+      }
+      out[u] = id;
+    }
+    if (MULT) asm volatile("" : "+v"(fields));  // really one register: not the W id words kept for their fields
+  };
+  auto read_ids = [&](int batch_idx) { read_batch(batch_idx, idx, mults_in); };
 
   const uint32_t row_bytes = (uint32_t)ldx * 4u;
   int k = grab();
-  int my_b = boundaries(k);
-  int nxt_idx = k < total ? first_ids(my_b, owned_decode(pl, wg, T, k, grp).rows, 0) : 0;
-  int nxt_idx1 = k < total ? first_ids(my_b, owned_decode(pl, wg, T, k, grp).rows, 1) : 0;
+  OwnedWork w = owned_decode(pl, wg, T, k, grp);
+  int e_begin = 0, e_end = 0;
+  hand_over(boundaries(w), w, e_begin, e_end);
+  int my_rel = rel_b;  // lane j of a group: boundary j of the group's rows (j <= rows), relative to e_begin
   while (k < total) {
-    const OwnedWork w = owned_decode(pl, wg, T, k, grp);
-    const int k_next = grab();
-    const int next_b = boundaries(k_next);  // in flight during this task's gathers
-    if (lag >= 0)
-      while (__hip_atomic_load(open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < w.phase) __builtin_amdgcn_s_sleep(1);
-    // the task that used these LDS rows in the phase before (this round's, or the last one of the round before)
-    while (__hip_atomic_load(&done[w.task], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < w.phase) __builtin_amdgcn_s_sleep(1);
-
-    const int nr = w.rows;
+    const int L = e_end - e_begin;  // the group's run: 0 without rows, or with rows that have no edge in this slice
     int col = (w.col_round * LPR + glane) * 4;
     const bool col_ok = col < F;
     if (!col_ok) col = 0;  // such a lane gathers column 0 and keeps its sums to itself
     const float* Xc = X + col;
     const uint32_t col_bytes = (uint32_t)col * 4u;
+    // A cold start (the first task of a wave, or a run before this one without edges): the prologue of the window.
+    if (L > 0 && !carried) {
+      read_ids(nxt_idx);
+#pragma unroll
+      for (int u = 0; u < W; ++u) v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+      mults = mults_in;
+    }
+    const int k_next = grab();
+    const OwnedWork w_next = owned_decode(pl, wg, T, k_next, grp);
+    const int next_b = boundaries(w_next);
+    int n_begin = 0, n_end = 0;  // the group's run in the next task
+    if (lag >= 0)
+      while (__hip_atomic_load(open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < w.phase) __builtin_amdgcn_s_sleep(1);
+    // the task that used these LDS rows in the phase before (this round's, or the last one of the round before)
+    while (__hip_atomic_load(&done[w.task], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < w.phase) __builtin_amdgcn_s_sleep(1);
+    const int first_ids = nxt_idx1;  // this run's batch 1 (owned_carry_start_batch), before the next run's replaces it
+    static_assert(owned_carry_start_batch() == 1, "nxt_idx1");
+    if (CARRY) hand_over(next_b, w_next, n_begin, n_end);
+
+    const int nr = w.rows;
     float4* slot = lds_rows + (size_t)w.lds_row * LPR + glane;
     // the segment sum of row r of the group joins the row's running sum
     auto commit = [&](int r, const float4& acc) {
@@ -226,14 +309,18 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
     };
     // The last slice's phase writes Y: dst_scale and the epilogue once per row, after the task's gathers — not inside
     // commit, where the scale, the mask and the addresses of Y would be live next to 8 gathered rows — from the sums
-    // this lane has just left in LDS.
+    // this lane has just left in LDS.  The scales were requested when the task was reserved and have arrived (my_ds): no load
+    // stands between the task's sums and the release of done[].
     auto write_rows = [&]() {
-      if (w.slice != kOwnedSlices - 1 || !col_ok) return;
+      if (w.slice != kOwnedSlices - 1) return;
       for (int r = 0; r < nr; ++r) {
+        float d = 0.f;
+        if (CARRY) d = __shfl(my_ds, gbase + r, kWave);  // (by every lane of the group)
+        if (!col_ok) continue;
         float4 t = slot[r * LPR];
-        const int64_t row = w.row0 + r;
+        const int64_t row = w.row_base + (w.lds_row + r);
         if (dst_scale != nullptr) {
-          const float d = dst_scale[row];
+          if (!CARRY) d = dst_scale[row];
           t.x *= d;
           t.y *= d;
           t.z *= d;
@@ -243,98 +330,123 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
       }
     };
 
-    if (nr > 0) {
-      const int e_begin = __shfl(my_b, gbase, kWave);
-      const int e_end = __shfl(my_b, gbase + nr, kWave);
-      int r = 0;
-      int row_end = __shfl(my_b, gbase + 1, kWave);
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (e_begin < e_end) {
-        // The rolling window (owned_window, dgmi_owned_common.h): W rows in flight from the prologue to the last group;
-        // the sum takes the edges in order, one at a time, exactly as the pair's gather does.
-        constexpr int W = kOwnedWindow;
-        static_assert(W <= 8 && kMultShift == 28 && LPR % W == 0, "at most eight 4-bit multiplicity fields, shifted down from bit 28");
-        const int L = e_end - e_begin;
-        float4 v[W];
-        int idx[W];  // the ids of a group's W issues, read at its top: an issue is a multiply and a load
-        // The multiplicity fields of the W rows in flight wait in one register, the next edge's in bits 32 - 4 W ..: a
-        // consumed field is shifted out, a new one comes in at bit 28.  Those of the W ids read at a group's top collect
-        // in a second register and replace the first after the group.
-        uint32_t mults = 0, mults_in = 0;
-        auto read_ids = [&](int batch_idx) {  // lanes 0 .. W - 1 of the group's id batch
-#pragma unroll
-          for (int u = 0; u < W; ++u) {
-            int id = __shfl(batch_idx, gbase + u, kWave);
-            if (MULT) {
-              mults_in = (mults_in >> 4) | ((uint32_t)id & ((uint32_t)kMultMax << kMultShift));
-              id &= kIdMask;
-            }
-            idx[u] = id;
-          }
-          if (MULT) asm volatile("" : "+v"(mults_in));  // really one register: not the W id words kept for their fields
-        };
-        auto add = [&](int u) {  // acc + x / fmaf(m, x, acc): the canonical step
-          if (MULT) {
-            const float m = (float)(((mults >> (32 - 4 * W)) & (uint32_t)kMultMax) + 1u);
-            mults >>= 4;
-            acc.x = fmaf(m, v[u].x, acc.x);
-            acc.y = fmaf(m, v[u].y, acc.y);
-            acc.z = fmaf(m, v[u].z, acc.z);
-            acc.w = fmaf(m, v[u].w, acc.w);
-          } else {
-            acc.x += v[u].x;
-            acc.y += v[u].y;
-            acc.z += v[u].z;
-            acc.w += v[u].w;
-          }
-        };
-        auto rows_before = [&](int p) {  // row(s) ended before edge p (empty rows commit zeros)
-          while (p >= row_end) {
-            commit(r, acc);
-            acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            ++r;
-            row_end = __shfl(my_b, gbase + r + 1, kWave);
-          }
-        };
-        read_ids(nxt_idx);
-        int ids = nxt_idx1;  // the id batch of the next issues
-#pragma unroll
-        for (int u = 0; u < W; ++u) v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
-        mults = mults_in;
-        // The scheduling barriers pin every gather right behind the consumption of the row it replaces: left alone, the
-        // scheduler sinks each load down to its use and two are in flight instead of W.
+    bool carry = false;             // whether the group hands its window over to its run in the next task
+    int r = 0;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (L > 0) {
+      // The rolling window (owned_window, dgmi_owned_common.h): W rows in flight from the first group of a run to its
+      // last; the sum takes the edges in order, one at a time, exactly as the pair's gather does.
+      int row_end = e_begin + __shfl(my_rel, gbase + 1, kWave);
+      auto add = [&](int u) {  // acc + x / fmaf(m, x, acc): the canonical step
+        if (MULT) {
+          const float m = (float)(((mults >> (32 - 4 * W)) & (uint32_t)kMultMax) + 1u);
+          mults >>= 4;
+          acc.x = fmaf(m, v[u].x, acc.x);
+          acc.y = fmaf(m, v[u].y, acc.y);
+          acc.z = fmaf(m, v[u].z, acc.z);
+          acc.w = fmaf(m, v[u].w, acc.w);
+        } else {
+          acc.x += v[u].x;
+          acc.y += v[u].y;
+          acc.z += v[u].z;
+          acc.w += v[u].w;
+        }
+      };
+      auto rows_before = [&](int p) {  // row(s) ended before edge p (empty rows commit zeros)
+        while (p >= row_end) {
+          commit(r, acc);
+          acc = make_float4(0.f, 0.f, 0.f, 0.f);
+          ++r;
+          row_end = e_begin + __shfl(my_rel, gbase + r + 1, kWave);
+        }
+      };
+      int ids = first_ids;  // the id batch of the next issues, whether the run starts warm or cold
+      // The scheduling barriers pin every gather right behind the consumption of the row it replaces: left alone, the
+      // scheduler sinks each load down to its use and two are in flight instead of W.
+      __builtin_amdgcn_sched_barrier(0);
+      int p0 = e_begin;
+      carry = CARRY && owned_carry(L, n_end - n_begin);
+      auto group = [&](int g) {  // group g (not the last of its run): W edges of the run, and something to issue
+        read_ids(ids);  // batch g + 1, requested W gathers ago or more
+        ids = indices[e_begin + owned_window_id_edge(owned_window_request_batch(g), glane, L)];  // unconditional: clamped
         __builtin_amdgcn_sched_barrier(0);
-        int p0 = e_begin;
-        for (int g = 0; p0 + W < e_end; ++g, p0 += W) {  // group g: W edges of the run, and something to issue
-          read_ids(ids);  // batch g + 1, requested W gathers ago or more
-          ids = indices[e_begin + owned_window_id_edge(owned_window_request_batch(g), glane, L)];  // unconditional: clamped
-          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int u = 0; u < W; ++u) {
+        for (int u = 0; u < W; ++u) {
+          rows_before(p0 + u);
+          add(u);
+          v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        mults = mults_in;
+      };
+      // Where this run and the group's run in the next task both have edges (owned_carry) the last group refills slot u,
+      // right behind its consumption, with edge u of that run — lane u of its batch 0 (owned_carry_slot_edge), the next
+      // task's column offset — and the next task starts with its window full.  These gathers touch neither LDS nor Y
+      // and wait for neither done[] nor the gate.  The batch is read behind group 0 (owned_carry_read_group), W gathers
+      // after its request; a run of one or two groups reads it before its last group, and waits.
+      // Groups 0 and 1 of a run of three groups or more stand in one straight line in front of the loop, the read between
+      // them: the form in which the compiler keeps the ring v[] in place (a single group in front of its rotated loop
+      // makes it copy a slot behind a vmcnt(0), and so does a read under a condition inside the loop).
+      static_assert(owned_carry_read_group(2 * W + 1) == 0 && owned_carry_read_group(2 * W) == -1, "behind group 0 of three or more");
+      int g = 0;
+      if (owned_carry_read_group(L) == 0) {
+        group(0);
+        p0 += W;
+        if (carry) read_batch(nxt_idx, nidx, nmults);
+        group(1);
+        p0 += W;
+        g = 2;
+      } else {
+        if (p0 + W < e_end) {
+          group(0);
+          p0 += W;
+          g = 1;
+        }
+        if (carry) read_batch(nxt_idx, nidx, nmults);  // a run of one or two groups: waits for the batch
+      }
+      for (; p0 + W < e_end; ++g, p0 += W) group(g);
+      // The last group: 1 .. W edges and nothing left to issue of this run.
+      const float* Xn = X;
+      uint32_t ncol_bytes = 0;
+      if (carry) {
+        int ncol = (w_next.col_round * LPR + glane) * 4;
+        if (ncol >= F) ncol = 0;
+        Xn = X + ncol;
+        ncol_bytes = (uint32_t)ncol * 4u;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (carry) {  // (a path of its own: one that issues under a condition would be waited for as if it had not)
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+          if (p0 + u < e_end) {  // group-uniform
             rows_before(p0 + u);
             add(u);
-            v[u] = ld_row<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
-            __builtin_amdgcn_sched_barrier(0);
           }
-          mults = mults_in;
+          v[u] = ld_row<OFF32>(X, Xn, nidx[u], ldx, row_bytes, ncol_bytes);
+          __builtin_amdgcn_sched_barrier(0);
         }
+        mults = nmults;
+      } else {  // the window drains
 #pragma unroll
-        for (int u = 0; u < W; ++u) {  // the last group: 1 .. W edges, nothing left to issue — the window drains
-          if (p0 + u < e_end) {        // group-uniform
+        for (int u = 0; u < W; ++u) {
+          if (p0 + u < e_end) {
             rows_before(p0 + u);
             add(u);
           }
         }
       }
+    }
+    if (nr > 0) {
       for (; r < nr; ++r) {  // the last non-empty row, then any trailing empty rows
         commit(r, acc);
         acc = make_float4(0.f, 0.f, 0.f, 0.f);
       }
       write_rows();
     }
-    // the next task's first ids, requested before this one is reported (its boundaries arrived long ago)
-    nxt_idx = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows, 0) : 0;
-    nxt_idx1 = k_next < total ? first_ids(next_b, owned_decode(pl, wg, T, k_next, grp).rows, 1) : 0;
+    // the draining form keeps nothing of the next task but its number across this one: decoded again, and its first
+    // ids requested, after the task's last row
+    const OwnedWork w_then = CARRY ? w_next : owned_decode(pl, wg, T, k_next, grp);
+    if (!CARRY) hand_over(next_b, w_then, n_begin, n_end);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
       __hip_atomic_store(&done[w.task], w.phase + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -345,7 +457,11 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
       }
     }
     k = k_next;
-    my_b = next_b;
+    w = w_then;
+    my_rel = rel_b;
+    e_begin = n_begin;
+    e_end = n_end;
+    carried = carry;
   }
 }
 
@@ -379,6 +495,16 @@ int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
   return 0;
 }
 
+// The built-in R's tasks-per-phase target of a class: kOwnedPhaseTasksMult for the two kNN-64 classes of the rule above,
+// which were measured with the hand-over (profiles/owned_carry/README.md: R = 3 instead of 4), kOwnedPhaseTasks for
+// every other product — also for ids with multiplicities of shapes nobody has measured.  (R does not enter the class.)
+int owned_class_phase_tasks(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+  const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return kOwnedPhaseTasksMult;
+  if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return kOwnedPhaseTasksMult;
+  return kOwnedPhaseTasks;
+}
+
 // Whether `wgs` workgroups of `threads` threads and `lds` bytes of dynamic LDS of this kernel are resident on one CU
 // together, by the runtime's occupancy query; asked once per kernel and LDS size.  A speed question only: a grid that
 // does not co-reside runs in two rounds and is still correct, so the caller then takes the one-workgroup form.
@@ -405,6 +531,7 @@ hipError_t launch_owned(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, 
                         hipStream_t s, bool* resident) {
   constexpr int kWgsPerCu = WAVES == kOwnedWaves ? 1 : 2;
   unsigned* arrive = reinterpret_cast<unsigned*>(a.planes);
+  const int workers = tuning().sliced_owned_workers > 0 && tuning().sliced_owned_workers < WAVES - 1 ? tuning().sliced_owned_workers : 0;
   *resident = true;
 #define DGMI_OWNED(V, O)                                                                                                  \
   do {                                                                                                                    \
@@ -426,7 +553,7 @@ hipError_t launch_owned(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, 
     }                                                                                                                     \
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave* WAVES), pl.lds_bytes, s, a.segptr, a.indices,              \
                        static_cast<const float*>(a.X), a.ldx, a.dst_scale, a.Y, a.ldy, a.n_dst, (int)a.F, pl, arrive, lag, \
-                       spin_ticks, a.ep);                                                                                 \
+                       spin_ticks, workers, a.ep);                                                                               \
     }                                                                                                                     \
   } while (0)
   if (a.id_mult) {
@@ -452,7 +579,12 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   if (grid < 1) return hipSuccess;
   const int lpr = sliced_lpr(a.F, a.n_src, a.n_slices, a.n_dst, a.full_width, a.n_keep, a.x_bytes, tune.sliced_lpr);
   // the one-workgroup plan names the class and is what a two-workgroup launch that cannot co-reside falls back to
-  const OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows);
+  // the plan with the general tasks-per-phase target names the class; the two measured kNN-64 classes then take theirs
+  OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows);
+  const int phase_tasks = a.n_dst < kOwnedMinRows ? kOwnedPhaseTasks
+                                                   : owned_class_phase_tasks(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float));
+  if (pl.ok && phase_tasks != kOwnedPhaseTasks)
+    pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks);
   if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return hipSuccess;
   // the arrive counters live in the first bytes of the caller's plane workspace (n_slices * n_dst * ldp floats)
   const auto arrive_fits = [&](const OwnedPlan& p) {

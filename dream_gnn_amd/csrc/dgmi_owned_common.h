@@ -1,7 +1,8 @@
 // dgmi_owned_common.h — the plan of the workgroup-owned form of the XCD-local SpMM (dgmi_owned.hip): which destination
 // rows a workgroup owns, how they are cut into rounds that fit its LDS, and which rows a task of a phase sums.  The
 // kernel, its launcher and the host test (tests/test_owned_plan_host.py) use owned_plan / owned_phase / owned_task and
-// nothing else.  At the end: the index arithmetic of the kernel's rolling gather window (owned_window_*).
+// nothing else.  At the end: the index arithmetic of the kernel's rolling gather window (owned_window_*) and of its
+// hand-over from task to task (owned_carry_*).
 //
 // Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
 // column tile (16 LPR bytes) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
@@ -22,6 +23,7 @@ constexpr int kOwnedPairWaves = 12;                 // the two-workgroups-per-CU
 constexpr int64_t kOwnedLdsRowBytes = 144 << 10;    // LDS budget of the partial rows (the CU has 160 KiB)
 constexpr int kOwnedMaxPhases = 128;                // per-phase words live in LDS and in the arrive counters
 constexpr int kOwnedPhaseTasks = 24;                // built-in R aims at this many tasks per phase
+constexpr int kOwnedPhaseTasksMult = 32;            // ... of the two kNN-64 classes (measured with the hand-over: profiles/owned_carry; owned_class_phase_tasks)
 constexpr int kOwnedMaxRows = 8;                    // built-in upper bound of R
 
 struct OwnedPlan {
@@ -51,11 +53,12 @@ struct OwnedTask {
 // shorter ones pay the start of a task — boundaries, then ids, then the first gathers — too often; a task still
 // practically never waits for its predecessor of the phase before); `lds_rows_cap` > 0: at most that many LDS rows
 // (forces row rounds); `wgs_per_cu`: 1 = one 16-wave workgroup per CU, 2 = two co-resident 12-wave workgroups, each with
-// half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way).
+// half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way);
+// `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes).
 __host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
 
 __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap,
-                                                int wgs_per_cu = 1) {
+                                                int wgs_per_cu = 1, int phase_tasks_target = kOwnedPhaseTasks) {
   OwnedPlan p{};
   p.ok = false;
   p.n_dst = n_dst;
@@ -75,7 +78,7 @@ __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lp
   int R = R_req;
   if (R <= 0) {
     // 1.6 tasks per worker wave: 24 for 15 workers, 18 for 11
-    const int phase_tasks = (kOwnedPhaseTasks * (owned_form_waves(wgs_per_cu) - 1) + kOwnedWorkers / 2) / kOwnedWorkers;
+    const int phase_tasks = (phase_tasks_target * (owned_form_waves(wgs_per_cu) - 1) + kOwnedWorkers / 2) / kOwnedWorkers;
     R = (p.round_rows + phase_tasks * p.G / 2) / (phase_tasks * p.G);  // rounded to nearest
     if (R > kOwnedMaxRows) R = kOwnedMaxRows;
   }
@@ -124,7 +127,8 @@ __host__ __device__ inline OwnedTask owned_task(const OwnedPlan& p, int64_t wg, 
 // The rolling gather window.  A lane group sums the L edges of its run (all the rows of its task, in order) with
 // W = kOwnedWindow gathers in flight: a prologue issues edges 0 .. W - 1; GROUP g then consumes edges g W .. g W + W - 1
 // in order and, right after consuming edge e, issues edge e + W into the registers e's row has just left — except in the
-// last group (owned_window_groups(L) - 1), which only consumes.  The ids arrive in BATCHES of W, whatever the lane-group
+// last group (owned_window_groups(L) - 1), which issues nothing of its own run (it refills for the next task's: the
+// hand-over below).  The ids arrive in BATCHES of W, whatever the lane-group
 // width: one register, in which lane l of the group holds the id of edge b W + l % W of batch b, clamped to the run's
 // last edge — so an edge issued past the end of the run gathers the run's last row again (an L1 hit, never one fixed
 // row) and is never consumed.  Batches 0 and 1 are requested before the run starts (during the task before).  At its
@@ -148,5 +152,29 @@ __host__ __device__ constexpr int owned_window_request_batch(int g) { return g +
 __host__ __device__ constexpr int owned_window_id_edge(int batch, int lane, int L) {
   return batch * kOwnedWindow + lane % kOwnedWindow < L ? batch * kOwnedWindow + lane % kOwnedWindow : L - 1;
 }
+
+// The hand-over.  A wave runs its tasks back to back, and a lane group's window survives the boundary between two of
+// them: in the last group of its run in task A (L_a edges) the group refills slot u, right after consuming it (or at
+// once, where the last group has no edge u), with edge u of its run in the wave's next task B (L_b edges) — B's id
+// batch 0, B's column offset, the same clamp.  B then starts with its window full and aligned at slot 0: no prologue,
+// its first group consumes at once, reads batch 1 out of the id register and requests batch 2 as any group does.  A
+// window is carried only between two runs that both have edges; every other run starts cold (the prologue), and
+// nothing is issued, and no id read, for a run without edges or past the last task.
+// B's batches 0 and 1 are requested at the top of A — B's boundaries, requested when B was reserved, are waited for
+// there, at a wave-uniform point, together with the gathers carried into A — and batch 0 is read behind A's group
+// owned_carry_read_group(L_a), W gathers after its request.  A run of one or two groups (-1) reads it right before its
+// last group, and waits.
+// The kernel and the host test (tests/test_owned_carry_host.py) take all of this from the functions below.
+__host__ __device__ constexpr bool owned_carry(int L_a, int L_b) { return L_a > 0 && L_b > 0; }
+
+// The edge of B (0-based in its run of L_b > 0 edges) that slot `u` of A's last group is refilled with; its id is lane
+// `u` of B's batch 0.
+__host__ __device__ constexpr int owned_carry_slot_edge(int u, int L_b) { return owned_window_id_edge(0, u, L_b); }
+
+// The group of A (not its last one) behind which B's batch 0 is read; -1: before the last group, with a wait.
+__host__ __device__ constexpr int owned_carry_read_group(int L_a) { return owned_window_groups(L_a) >= 3 ? 0 : -1; }
+
+// The id batch of B that its id register holds when a run starts (carried or cold): the one its group 0 reads.
+__host__ __device__ constexpr int owned_carry_start_batch() { return owned_window_issue_batch(0); }
 
 }  // namespace dgmi
