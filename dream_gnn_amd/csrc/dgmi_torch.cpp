@@ -89,7 +89,10 @@ struct Keep {
   int32_t n = 0;
 };
 
-Keep keep_of(const OptTensor& eid, const OptTensor& keep, int64_t nnz, const Tensor& like) {
+// `for_product`: the descriptions go to a product launch.  A layout without edges has nothing to drop, and its empty eid
+// tensor has no storage — a null pointer, which the C ABI refuses beside a description: such a product runs un-dropped (a
+// row shard that owns no edge, dropped by the step's description like every other).
+Keep keep_of(const OptTensor& eid, const OptTensor& keep, int64_t nnz, const Tensor& like, bool for_product = true) {
   Keep k;
   if (!keep.has_value() || !keep->defined()) return k;
   TORCH_CHECK(keep->scalar_type() == at::kInt && keep->is_contiguous() && keep->dim() == 2 && keep->size(1) == 8,
@@ -99,6 +102,7 @@ Keep keep_of(const OptTensor& eid, const OptTensor& keep, int64_t nnz, const Ten
   check(*eid, at::kInt, 1, "eid", like);
   check_dev(*keep, "keep");
   TORCH_CHECK(eid->numel() == nnz, "eid has ", eid->numel(), " entries, the layout has ", nnz, " edges");
+  if (for_product && nnz == 0) return k;
   k.eid = eid->data_ptr<int32_t>();
   k.table = reinterpret_cast<const uint32_t*>(keep->data_ptr<int32_t>());
   k.n = (int32_t)keep->size(0);
@@ -792,7 +796,7 @@ std::tuple<Tensor, Tensor, Tensor> compact_layout(const Tensor& ptr, const Tenso
   check(indices, at::kInt, 1, "indices", ptr);
   const int64_t nnz = indices.numel();
   check_opt(vals, at::kFloat, nnz, "vals", ptr);
-  const Keep k = keep_of(eid, keep, nnz, ptr);
+  const Keep k = keep_of(eid, keep, nnz, ptr, false);
   TORCH_CHECK(k.n > 0, "compact_layout needs at least one subset description");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(ptr.device());
   Tensor ptr_out = at::empty_like(ptr), indices_out = at::empty_like(indices);
