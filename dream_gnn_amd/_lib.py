@@ -119,6 +119,11 @@ GIVEN_SIGNATURES = {
                                                    ctypes.c_size_t, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/dgmi_layout.h (a seventh table, for the same reason).
+LAYOUT_SIGNATURES = {
+    "dgmi_sliced_layout_slices": (ctypes.c_int32, [_i64, _i64, _i64, ctypes.c_int32]),
+}
+
 
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
@@ -132,8 +137,8 @@ def _load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
                               + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
-                              + list(GIVEN_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the six headers declare
+                              + list(GIVEN_SIGNATURES.items()) + list(LAYOUT_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the seven headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()
@@ -162,6 +167,12 @@ torch_ops = _load_torch_ops()
 def set_tuning(name: str, value: int) -> None:
     """Override one launch parameter of the library (``dgmi_set_tuning``; measurement tools and one test)."""
     check(lib.dgmi_set_tuning(name.encode(), int(value)), "dgmi_set_tuning(%s)" % name)
+
+
+def sliced_layout_slices(n_dst: int, n_src: int, F: int, id_mult: bool = False) -> int:
+    """Source slices of the layout a plain fp32 XCD-local product of this shape should be given
+    (``dgmi_sliced_layout_slices``: 8 but for the measured class; host arithmetic, no launch)."""
+    return int(lib.dgmi_sliced_layout_slices(int(n_dst), int(n_src), int(F), 1 if id_mult else 0))
 
 
 def check(status: int, what: str) -> None:

@@ -8,6 +8,7 @@
 #include "dgmi.h"
 #include "dgmi_bf16.h"
 #include "dgmi_keep.h"
+#include "dgmi_layout.h"
 #include "dgmi_kernels.h"
 #include "dgmi_tuning.h"
 
@@ -42,6 +43,7 @@ Tuning& tuning() {
     v.sliced_owned_rows = (int)env_ll("DGMI_SLICED_OWNED_ROWS", 0);
     v.sliced_owned_lds_rows = env_ll("DGMI_SLICED_OWNED_LDS_ROWS", 0);
     v.sliced_owned_workers = (int)env_ll("DGMI_SLICED_OWNED_WORKERS", 0);
+    v.sliced_owned_slices = (int)env_ll("DGMI_SLICED_OWNED_SLICES", 0);
     v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
     v.sliced_owned_spin_ticks = env_ll("DGMI_SLICED_OWNED_SPIN_TICKS", 0);
     v.select_window_min = env_ll("DGMI_SELECT_WINDOW_MIN", 0);
@@ -73,6 +75,7 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_owned_rows") == 0) t.sliced_owned_rows = (int)value;
   else if (strcmp(name, "sliced_owned_lds_rows") == 0) t.sliced_owned_lds_rows = value;
   else if (strcmp(name, "sliced_owned_workers") == 0) t.sliced_owned_workers = (int)value;
+  else if (strcmp(name, "sliced_owned_slices") == 0) t.sliced_owned_slices = (int)value;
   else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;
   else if (strcmp(name, "sliced_owned_spin_ticks") == 0) t.sliced_owned_spin_ticks = value;
   else if (strcmp(name, "select_window_min") == 0) t.select_window_min = value;
@@ -380,6 +383,10 @@ DGMI_API int dgmi_spmm_sliced_bf16(const int32_t* segptr, const int32_t* indices
   return spmm_sliced(segptr, indices, vals, eid, keep, n_keep, X, 2, ldx, nullptr, dst_scale, Y, ldy, n_dst, n_src, F,
                      n_slices, column_passes, id_multiplicity, planes, planes_bytes, act, act_slope, out_mask, ld_mask,
                      out_mask_scale, stream);
+}
+
+DGMI_API int32_t dgmi_sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, int32_t id_multiplicity) {
+  return dgmi::sliced_layout_slices(n_dst, n_src, F, id_multiplicity == 1);
 }
 
 DGMI_API int dgmi_gather_concat_f32(const int32_t* src, const int32_t* dst, int64_t E, const float* A,

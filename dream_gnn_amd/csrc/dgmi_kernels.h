@@ -163,6 +163,8 @@ struct SlicedArgs {
 hipError_t row_multiplicity_f32(const int32_t* indptr, const float* vals, int64_t n_rows, float rel_tol, float* row_scale,
                                 int32_t* mult, int32_t* fail, hipStream_t s);
 hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s);
+// the slice count of the layout a plain fp32 product of this shape should be given (dgmi_owned.hip; include/dgmi_layout.h)
+int sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, bool id_mult);
 
 // The same product gathering from a bf16 table (dgmi_sliced_bf16.hip): x_bytes == 2, F and ldx multiples of 8, no source
 // scale (an error).  Planes, dst_scale, Y: fp32.

@@ -2,12 +2,15 @@
 //
 // The pair (dgmi_sliced.hip) pins each XCD to one slice of the feature table, so every destination row comes out in 8
 // pieces that go through 8 planes of scratch and a second launch.  Here one persistent workgroup per CU owns a
-// contiguous block of destination rows and walks the 8 slices one after the other, in order, over the SAME slice-major
-// layout; the running row sums stay in its LDS and Y is written once, by the last slice's phase.  No atomics: the unit
-// of work is a whole (row, slice) segment — one lane group sums it in registers exactly as the pair's gather does
-// (canonical in-order sum from +0) and commits it to the row's LDS slot with one plain 16-byte read-modify-write per
-// lane; only one lane group ever touches a given (row, phase).  The row sum takes its 8 segment sums in slice order,
-// ((s0 + s1) + s2) + ..., dst_scale and the epilogue once: bit-identical to the pair on the same layout.
+// contiguous block of destination rows and walks the slices one after the other, in order, over the SAME slice-major
+// layout; the running row sums stay in its LDS and Y is written once, by the last slice's phase.  Nothing binds a
+// workgroup to an XCD, so the layout may have any number S of slices the builders make (OwnedPlan::slices; 8 in the
+// text below): where 8 slices of a table do not fit an L2 at full width, 16 do (dgmi_sliced_layout_slices, at the end).
+// No atomics: the unit of work is a whole (row, slice) segment — one lane group sums it in registers exactly as the
+// pair's gather does (canonical in-order sum from +0) and commits it to the row's LDS slot with one plain 16-byte
+// read-modify-write per lane; only one lane group ever touches a given (row, phase).  The row sum takes its S segment
+// sums in slice order, ((s0 + s1) + s2) + ..., dst_scale and the epilogue once: bit-identical to the pair on the same
+// layout.
 //
 // The plan (rows per workgroup, rounds, phases, tasks): dgmi_owned_common.h.  Inside a workgroup the 15 worker waves
 // take tasks from one LDS counter, phase-major then row-major; a wave reserves its next task (and requests that task's
@@ -52,6 +55,7 @@
 // kernel is short of waves (12 instead of 16 per CU: +17-23 %), yet 512 free-running workgroups drift over more slices
 // than 256 and lose in L2 misses more than the waves return, so the built-in rule selects the second form for no class.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <map>
@@ -71,6 +75,8 @@ constexpr int64_t kOwnedMinRows = 32768;   // built-in rule: below, a workgroup 
 // Built-in gate: none.  A closed gate drains the workgroup — a task lives ~5 us of a ~15 us phase — so lag 0 costs
 // 35-45 % and lag 1 25-30 % of a product, far more than the L2 hits it buys (profiles/owned_rows/README.md).
 constexpr int kOwnedLag = -1;
+constexpr int kOwnedWideSlices = 16;       // the slice count of the one class whose layout is not the pair's (dgmi_sliced_layout_slices)
+constexpr int kOwnedAssumedCus = 256;      // workgroups the layout rule plans for where no device can be asked (MI355X)
 
 struct OwnedWork {  // task k of a workgroup, decoded (wave-uniform except lds_row / rows: per lane group)
   int phase, task, slice, col_round;
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
   };
   // lane j of a group holds dst_scale of the group's row j: only the last slice's phase, which writes Y, asks for it
   auto scales = [&](const OwnedWork& t) {
-    if (!CARRY || dst_scale == nullptr || t.slice != kOwnedSlices - 1 || t.rows == 0) return 0.f;
+    if (!CARRY || dst_scale == nullptr || t.slice != pl.slices - 1 || t.rows == 0) return 0.f;
     return dst_scale[t.row_base + (t.lds_row + (glane < t.rows ? glane : t.rows - 1))];
   };
   // The hand-over point of a task, WAVE-UNIFORM and right behind the wait for done[]: the boundaries `b` of the NEXT
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(kWave* WAVES, WAVES == kOwnedWaves ? 4 : 6) void sp
     // this lane has just left in LDS.  The scales were requested when the task was reserved and have arrived (my_ds): no load
     // stands between the task's sums and the release of done[].
     auto write_rows = [&]() {
-      if (w.slice != kOwnedSlices - 1) return;
+      if (w.slice != pl.slices - 1) return;
       for (int r = 0; r < nr; ++r) {
         float d = 0.f;
         if (CARRY) d = __shfl(my_ds, gbase + r, kWave);  // (by every lane of the group)
@@ -483,15 +489,22 @@ int device_cus() {
 //  - with the rolling gather window (profiles/owned_window/README.md) both kNN-64 classes: the half-width 100 000-node
 //    one (two column rounds, one row round, 51 MB table: -10 %) and the full-width 50 000-node one (one column round, one
 //    row round: -7 %).
-// The two-pass unit-value products (100 000 sources -> 50 000 rows) are within a spread of the pair: they stay on it.
+// The two-pass unit-value products (100 000 sources -> 50 000 rows) are within a spread of the pair on the 8-slice layout
+// and stay on it there.  On a layout of 16 slices (dgmi_sliced_layout_slices below; profiles/owned_slices/README.md) a
+// slice of their table fits an L2 at full width, and their plan is the first class's: one column round, one row round,
+// 16 phases.
+// The measured classes are classes of a slice count: the first three of 8 slices, the last of 16.
 // `pl`: the plan of one workgroup per CU, which names the class.  0 = the pair, 1 = one 16-wave workgroup per CU,
 // 2 = two 12-wave workgroups per CU.  No class takes 2: forced for all 8 products of the step it ran every one of them
 // 30-35 % slower than the pair (profiles/owned_wgs/README.md); it stays behind sliced_owned_wgs = 2.
 int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
   const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
-  if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return 1;
-  if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return 1;
-  if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return 1;
+  if (pl.slices == kOwnedSlices) {
+    if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return 1;
+    if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return 1;
+    if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return 1;
+  }
+  if (pl.slices == kOwnedWideSlices && pl.col_rounds == 1 && pl.row_rounds == 1 && !id_mult && mib(48, 64)) return 1;
   return 0;
 }
 
@@ -500,6 +513,7 @@ int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
 // every other product — also for ids with multiplicities of shapes nobody has measured.  (R does not enter the class.)
 int owned_class_phase_tasks(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
   const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (pl.slices != kOwnedSlices) return kOwnedPhaseTasks;
   if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return kOwnedPhaseTasksMult;
   if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return kOwnedPhaseTasksMult;
   return kOwnedPhaseTasks;
@@ -571,7 +585,7 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   *taken = false;
   const Tuning& tune = tuning();
   if (tune.sliced_owned == 0) return hipSuccess;
-  if (a.x_bytes != 4 || a.vals != nullptr || a.src_scale != nullptr || a.n_keep != 0 || a.n_slices != kOwnedSlices ||
+  if (a.x_bytes != 4 || a.vals != nullptr || a.src_scale != nullptr || a.n_keep != 0 || a.n_slices < 1 || a.n_slices > kOwnedMaxSlices ||
       tune.sliced_chunk_rows > 0 || a.chunk_rows < a.n_dst || a.n_dst == 0 || a.F == 0)
     return hipSuccess;
   // a forced grid counts workgroups, whichever form runs them
@@ -580,11 +594,12 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   const int lpr = sliced_lpr(a.F, a.n_src, a.n_slices, a.n_dst, a.full_width, a.n_keep, a.x_bytes, tune.sliced_lpr);
   // the one-workgroup plan names the class and is what a two-workgroup launch that cannot co-reside falls back to
   // the plan with the general tasks-per-phase target names the class; the two measured kNN-64 classes then take theirs
-  OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows);
+  const int slices = (int)a.n_slices;
+  OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, kOwnedPhaseTasks, slices);
   const int phase_tasks = a.n_dst < kOwnedMinRows ? kOwnedPhaseTasks
                                                    : owned_class_phase_tasks(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float));
   if (pl.ok && phase_tasks != kOwnedPhaseTasks)
-    pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks);
+    pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks, slices);
   if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return hipSuccess;
   // the arrive counters live in the first bytes of the caller's plane workspace (n_slices * n_dst * ldp floats)
   const auto arrive_fits = [&](const OwnedPlan& p) {
@@ -601,7 +616,7 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   bool resident = true;
   if (form == 2) {
     const int64_t grid2 = tune.sliced_owned_grid > 0 ? grid : 2 * grid;
-    const OwnedPlan pl2 = owned_plan(a.n_dst, a.F, lpr, grid2, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 2);
+    const OwnedPlan pl2 = owned_plan(a.n_dst, a.F, lpr, grid2, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 2, kOwnedPhaseTasks, slices);
     if (pl2.ok && pl2.lds_bytes <= (size_t)(80 << 10) && arrive_fits(pl2)) {
       hipError_t err;
       switch (lpr) {
@@ -619,6 +634,28 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
     case 32: return launch_owned<32, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
     default: return launch_owned<64, kOwnedWaves>(a, pl, grid, off32, lag, spin, s, &resident);
   }
+}
+
+// The slice count of the layout a plain fp32 product of this shape should be given (include/dgmi_layout.h).  8 — the
+// pair's binding of a slice to an XCD — for everything but the class of owned_class_form that was measured on 16
+// slices; Tuning::sliced_owned_slices forces a count for every product the form can plan.  It asks the launcher's own
+// sliced_lpr / owned_plan / owned_class_form with the slice count in question, so a layout is only ever made wide for
+// a product spmm_owned_try then takes.
+int sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, bool id_mult) {
+  const Tuning& tune = tuning();
+  if (n_dst < 1 || n_src < 1 || F < 1 || F % 4 != 0 || tune.sliced_owned == 0 || tune.sliced_chunk_rows > 0) return kOwnedSlices;
+  const int forced = tune.sliced_owned_slices;
+  const int slices = forced > 0 ? (forced < kOwnedMaxSlices ? forced : kOwnedMaxSlices) : kOwnedWideSlices;
+  if (slices == kOwnedSlices) return kOwnedSlices;
+  // the layout's row boundaries are int32 words, and the launcher chunks planes beyond 4 GiB (dgmi_api.hip): the pair's then
+  if (n_dst * slices >= INT32_MAX || n_dst * slices * F * (int64_t)sizeof(float) > ((int64_t)4096 << 20)) return kOwnedSlices;
+  const int64_t grid = tune.sliced_owned_grid > 0 ? tune.sliced_owned_grid : (device_cus() > 0 ? device_cus() : kOwnedAssumedCus);
+  const int lpr = sliced_lpr(F, n_src, slices, n_dst, false, 0, 4, tune.sliced_lpr);
+  const OwnedPlan pl = owned_plan(n_dst, F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, kOwnedPhaseTasks, slices);
+  if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return kOwnedSlices;
+  if (forced > 0) return slices;
+  if (n_dst < kOwnedMinRows) return kOwnedSlices;
+  return owned_class_form(pl, id_mult, n_src * F * (int64_t)sizeof(float)) == 1 ? slices : kOwnedSlices;
 }
 
 }  // namespace dgmi

@@ -6,8 +6,9 @@
 //
 // Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
 // column tile (16 LPR bytes) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
-// (column round, row round, slice), slices 0 .. 7 innermost and in order: the row sums take their 8 segment sums in the
-// order the plane reduce adds the planes.  A phase is cut into TASKS of G R consecutive rows of the round — one wave,
+// (column round, row round, slice), slices 0 .. S - 1 innermost and in order: the row sums take their S segment sums in
+// the order the plane reduce adds the planes.  S is the layout's slice count, a field of the plan (8 unless the caller
+// says otherwise): nothing binds a workgroup to an XCD, so the form walks as many slices as the layout has.  A phase is cut into TASKS of G R consecutive rows of the round — one wave,
 // R rows for each of its G = 64 / LPR lane groups; task t of every phase of a round covers the same LDS rows.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,7 +17,8 @@
 
 namespace dgmi {
 
-constexpr int kOwnedSlices = 8;                     // the form exists for 8 slices only (one per XCD)
+constexpr int kOwnedSlices = 8;                     // the slice count of a plan made without one (one slice per XCD, as the pair's layouts)
+constexpr int kOwnedMaxSlices = 64;                 // what the layout builders take
 constexpr int kOwnedWaves = 16;                     // waves per workgroup: 15 workers and the toucher
 constexpr int kOwnedWorkers = kOwnedWaves - 1;
 constexpr int kOwnedPairWaves = 12;                 // the two-workgroups-per-CU form: 2 x (11 workers and a toucher)
@@ -30,6 +32,7 @@ struct OwnedPlan {
   bool ok;             // false: the form does not take this product (too many phases, nothing to do)
   int lpr, G, R;       // lane-group width, lane groups per wave, rows per lane group and task
   int col_rounds, row_rounds, phases;
+  int slices;          // source slices of the layout: the innermost index of a phase
   int64_t wg_rows;     // B
   int64_t active;      // workgroups that own at least one row: 0 .. active - 1
   int round_rows;      // rows of a workgroup in one row round = LDS rows
@@ -54,16 +57,21 @@ struct OwnedTask {
 // practically never waits for its predecessor of the phase before); `lds_rows_cap` > 0: at most that many LDS rows
 // (forces row rounds); `wgs_per_cu`: 1 = one 16-wave workgroup per CU, 2 = two co-resident 12-wave workgroups, each with
 // half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way);
-// `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes).
+// `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes);
+// `slices`: the slice count of the layout, 1 .. kOwnedMaxSlices.
 __host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
 
 __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap,
-                                                int wgs_per_cu = 1, int phase_tasks_target = kOwnedPhaseTasks) {
+                                                int wgs_per_cu = 1, int phase_tasks_target = kOwnedPhaseTasks,
+                                                int slices = kOwnedSlices) {
   OwnedPlan p{};
   p.ok = false;
   p.n_dst = n_dst;
-  if (n_dst < 1 || F < 1 || grid < 1 || (wgs_per_cu != 1 && wgs_per_cu != 2) || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64)) return p;
+  if (n_dst < 1 || F < 1 || grid < 1 || (wgs_per_cu != 1 && wgs_per_cu != 2) || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64) ||
+      slices < 1 || slices > kOwnedMaxSlices)
+    return p;
   p.lpr = lpr;
+  p.slices = slices;
   p.G = 64 / lpr;
   p.col_rounds = (int)((F + 4 * lpr - 1) / (4 * lpr));
   p.wg_rows = (n_dst + grid - 1) / grid;
@@ -71,10 +79,10 @@ __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lp
   int64_t fit = kOwnedLdsRowBytes / wgs_per_cu / (16 * lpr);
   if (lds_rows_cap > 0 && lds_rows_cap < fit) fit = lds_rows_cap;
   const int64_t rounds = (p.wg_rows + fit - 1) / fit;
-  if (rounds * p.col_rounds * kOwnedSlices > kOwnedMaxPhases) return p;
+  if (rounds * p.col_rounds * slices > kOwnedMaxPhases) return p;
   p.row_rounds = (int)rounds;
   p.round_rows = (int)((p.wg_rows + rounds - 1) / rounds);  // <= fit
-  p.phases = p.col_rounds * p.row_rounds * kOwnedSlices;
+  p.phases = p.col_rounds * p.row_rounds * slices;
   int R = R_req;
   if (R <= 0) {
     // 1.6 tasks per worker wave: 24 for 15 workers, 18 for 11
@@ -112,8 +120,8 @@ __host__ __device__ inline int owned_wg_tasks(const OwnedPlan& p, int64_t wg) {
 }
 
 __host__ __device__ inline OwnedPhase owned_phase(const OwnedPlan& p, int phase) {
-  const int cq = phase / kOwnedSlices;
-  return OwnedPhase{cq / p.row_rounds, cq % p.row_rounds, phase % kOwnedSlices};
+  const int cq = phase / p.slices;
+  return OwnedPhase{cq / p.row_rounds, cq % p.row_rounds, phase - cq * p.slices};
 }
 
 // Lane group `group` (0 .. G - 1) of task slot `task` in row round `row_round` of workgroup `wg`.

@@ -283,10 +283,14 @@ class SlicedCSR:
         """The pass moves 2 x table bytes (3.4e-13 s per byte measured), the in-kernel scale gather costs 2.7e-12 s
         per edge and column pass: pre-scale when the table is below ~8 bytes per edge-pass (config 4: 26-51 MB against
         10 M edges x 1-2 passes; a 400 MB table with 6 M edges keeps the in-kernel gather — the kernel-choice sweep)."""
+        return self._prescale_rule(table_bytes, one_pass, self.n_dst, self.n_slices, int(self.indices.shape[0]))
+
+    @staticmethod
+    def _prescale_rule(table_bytes: int, one_pass: bool, n_dst: int, n_slices: int, nnz: int) -> bool:
         if table_bytes < PRESCALE_MIN_TABLE_BYTES:
             return False
-        passes = 1 if one_pass or self.n_dst < 32768 or table_bytes // self.n_slices <= (4 << 20) else 2  # the launcher's column-pass rule
-        return table_bytes <= 6 * int(self.indices.shape[0]) * passes
+        passes = 1 if one_pass or n_dst < 32768 or table_bytes // n_slices <= (4 << 20) else 2  # the launcher's column-pass rule
+        return table_bytes <= 6 * nnz * passes
 
     def spmm(self, X, src_scale=None, dst_scale=None, out=None, vals=_DEFAULT, keep=None, epi=None, full_width=False,
              indices=None, id_mult=None, gather_dtype=None):
@@ -400,7 +404,7 @@ class _Structure:
     """Everything about a CSRGraph that depends on the edge list only (shared by value views)."""
 
     __slots__ = ("n_dst", "n_src", "dst", "src", "indptr", "indices", "eid", "plan", "planned", "t",
-                 "sliced", "sliced_t", "regular", "regular_t", "validated", "split", "split_t", "max_deg", "max_deg_t")
+                 "sliced", "sliced_t", "wide", "regular", "regular_t", "validated", "split", "split_t", "max_deg", "max_deg_t")
 
 
 # Rows longer than this are cut into virtual rows before the XCD-local kernel sees them (power-law
@@ -542,6 +546,7 @@ class CSRGraph:
         S.indptr, S.indices, S.eid, flag = csr_from_coo(S.dst, S.src, S.n_dst, S.n_src, return_flag=True)
         S.planned = planned
         S.t = S.sliced = S.sliced_t = S.split = S.split_t = None
+        S.wide = {}  # (transposed, n_slices) -> an XCD-sliced layout of another slice count than sliced / sliced_t have (_layout_of)
         S.max_deg = S.max_deg_t = None  # longest row of the CSR / of the transposed CSR, once a readback has told
         S.validated = bool(check_range)
         # `regular`: no destination row is extremely long, so the XCD-local kernel (which walks a
@@ -888,17 +893,7 @@ class CSRGraph:
         """The plain XCD-local product with a bf16 gather: ``gathered_scale`` multiplies the gathered rows (folded into
         the conversion of a float32 ``X``), ``out_scale`` the output rows (applied by the plane reduce)."""
         S = self._S
-        if transposed:
-            name = "sliced_t"
-            if S.sliced_t is None:
-                indptr_t, indices_t, eid_t, _ = self._t_struct()
-                S.sliced_t = SlicedCSR.from_csr(indptr_t, indices_t, eid_t, S.n_src, S.n_dst)
-            layout = S.sliced_t
-        else:
-            name = "sliced"
-            if S.sliced is None:
-                S.sliced = SlicedCSR.from_csr(S.indptr, S.indices, S.eid, S.n_dst, S.n_src)
-            layout = S.sliced
+        name, layout = self._layout_of(transposed)  # the pair's 8 slices: the owned form gathers no bf16
         mult = self._mult_ids(name, layout)
         if mult is not None:  # the scale of `scale x multiplicity` values lands on the output rows or on the gathered rows
             if (mult[0] == "row") != transposed:
@@ -922,6 +917,53 @@ class CSRGraph:
         return layout.spmm(X, gathered_scale, out_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi,
                            gather_dtype=gd)
 
+    def _plain_layout(self, transposed: bool, F: int, gathered_scale):
+        """``(name, layout)`` of the plain float32 XCD-local product of width ``F``; ``name`` keys this view's per-layout
+        values, id words and compacted copies.
+
+        The library says how many source slices the layout of a product should have (``dgmi_sliced_layout_slices``: 8
+        unless the product is of the class the workgroup-owned form runs faster on 16, or ``sliced_owned_slices``
+        forces a count).  Only a product that form can take is asked about: unit values or multiplicities in the id
+        words, no edge dropout evaluated inside the kernel (a compacted view runs the plain kernels), and a scale on
+        the gathered rows only where the pre-scale pass takes it out of the kernel.  Every other product — and the bf16
+        gather — runs the pair on the 8-slice layout, as does every shape the library answers 8 for.  Which layout a
+        product runs on depends on the product alone, never on what the graph has built before (:meth:`_layout_of`)."""
+        S = self._S
+        n_rows, n_cols = (S.n_src, S.n_dst) if transposed else (S.n_dst, S.n_src)
+        n = SlicedCSR.N_SLICES
+        mf = self._mult_form()
+        if (self._coo_vals is None or mf is not None) and (self._keep is None or COMPACT_DROPPED):
+            n = _lib.sliced_layout_slices(n_rows, n_cols, F, mf is not None)
+            scaled = gathered_scale is not None or (mf is not None and (mf[0] == "row") == transposed)
+            if n != SlicedCSR.N_SLICES and scaled and not SlicedCSR._prescale_rule(n_cols * F * 4, False, n_rows, n, self.nnz):
+                n = SlicedCSR.N_SLICES  # the scale would be gathered inside the kernel: the pair's product
+        return self._layout_of(transposed, n)
+
+    def _layout_of(self, transposed: bool, n_slices: int = SlicedCSR.N_SLICES):
+        """``(name, layout)``: the XCD-sliced layout of ``n_slices`` source slices, built on first use.  The first layout
+        a graph builds per direction sits in ``sliced`` / ``sliced_t`` (name ``"sliced"`` / ``"sliced_t"``), one of
+        another slice count beside it in ``wide`` (name ``"sliced/<n>"``): a graph whose products all run on one
+        layout holds one."""
+        S = self._S
+        base = "sliced_t" if transposed else "sliced"
+        first = S.sliced_t if transposed else S.sliced
+        if first is not None and first.n_slices == n_slices:
+            return base, first
+        layout = None if first is None else S.wide.get((transposed, n_slices))
+        if layout is None:
+            if transposed:
+                indptr_t, indices_t, eid_t, _ = self._t_struct()
+                layout = SlicedCSR.from_csr(indptr_t, indices_t, eid_t, S.n_src, S.n_dst, n_slices)
+            else:
+                layout = SlicedCSR.from_csr(S.indptr, S.indices, S.eid, S.n_dst, S.n_src, n_slices)  # one partition pass, no sort
+            if first is not None:
+                S.wide[(transposed, n_slices)] = layout
+            elif transposed:
+                S.sliced_t = layout
+            else:
+                S.sliced = layout
+        return (base if first is None else "%s/%d" % (base, n_slices)), layout
+
     def spmm(self, X, src_scale=None, dst_scale=None, out=None, epi=None, gather_dtype=None):
         """``diag(dst_scale) A diag(src_scale) X`` (no autograd).  Picks the XCD-local sliced kernel when the
         feature table is a few L2s large and the graph is regular, else the planned kernel.  ``epi``: output epilogue
@@ -936,21 +978,19 @@ class CSRGraph:
         long_rows = X.dim() == 2 and bool(S.regular) and self._few_long_rows(X.shape[1], S.n_dst, S.n_src)
         if (X.dim() == 2 and not long_rows and self._use_sliced(X.shape[1], S.n_dst, S.n_src, S.regular)
                 and _sliced_ok(X, out)):
-            if S.sliced is None:
-                S.sliced = SlicedCSR.from_csr(S.indptr, S.indices, S.eid, S.n_dst, S.n_src)  # one partition pass, no sort
-            mult = self._mult_ids("sliced", S.sliced)
+            name, layout = self._plain_layout(False, X.shape[1], src_scale)
+            mult = self._mult_ids(name, layout)
             if mult is not None:  # values = scale x multiplicity: a destination (D^-1 M) or a source (M D^-1) scale
                 if mult[0] == "row":
                     dst_scale = self._fold(mult[1], dst_scale)
                 else:
                     src_scale = self._fold(mult[1], src_scale)
-            c = self._compacted("sliced", S.sliced, mult)
+            c = self._compacted(name, layout, mult)
             if c is not None:
                 return c.spmm(X, src_scale, dst_scale, out, epi=epi)
             if mult is not None:
-                return S.sliced.spmm(X, src_scale, dst_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2], id_mult=True)
-            return S.sliced.spmm(X, src_scale, dst_scale, out, vals=self._vals_for("sliced", S.sliced.eid), keep=self._keep,
-                                 epi=epi)
+                return layout.spmm(X, src_scale, dst_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2], id_mult=True)
+            return layout.spmm(X, src_scale, dst_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi)
         if X.dim() == 2 and _sliced_ok(X, out) and (self._use_split(X.shape[1], S.n_dst, S.n_src, S.regular) or (
                 long_rows and self._use_sliced(X.shape[1], S.n_dst, S.n_src, S.regular))):
             if S.split is None:
@@ -974,21 +1014,19 @@ class CSRGraph:
         long_rows = dY.dim() == 2 and bool(S.regular_t) and self._few_long_rows(dY.shape[1], S.n_src, S.n_dst)
         if (dY.dim() == 2 and not long_rows and self._use_sliced(dY.shape[1], S.n_src, S.n_dst, S.regular_t)
                 and _sliced_ok(dY, out)):
-            if S.sliced_t is None:
-                S.sliced_t = SlicedCSR.from_csr(indptr_t, indices_t, eid_t, S.n_src, S.n_dst)
-            mult = self._mult_ids("sliced_t", S.sliced_t)
+            name, layout = self._plain_layout(True, dY.shape[1], dst_scale)
+            mult = self._mult_ids(name, layout)
             if mult is not None:  # (D^-1 M)^T = M^T D^-1: the scale multiplies the gathered (destination-node) rows; (M D^-1)^T: the output rows
                 if mult[0] == "row":
                     dst_scale = self._fold(mult[1], dst_scale)
                 else:
                     src_scale = self._fold(mult[1], src_scale)
-            c = self._compacted("sliced_t", S.sliced_t, mult)
+            c = self._compacted(name, layout, mult)
             if c is not None:
                 return c.spmm(dY, dst_scale, src_scale, out)
             if mult is not None:
-                return S.sliced_t.spmm(dY, dst_scale, src_scale, out, vals=None, keep=self._keep, indices=mult[2], id_mult=True)
-            return S.sliced_t.spmm(dY, dst_scale, src_scale, out, vals=self._vals_for("sliced_t", S.sliced_t.eid),
-                                   keep=self._keep)
+                return layout.spmm(dY, dst_scale, src_scale, out, vals=None, keep=self._keep, indices=mult[2], id_mult=True)
+            return layout.spmm(dY, dst_scale, src_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep)
         if dY.dim() == 2 and _sliced_ok(dY, out) and (self._use_split(dY.shape[1], S.n_src, S.n_dst, S.regular_t) or (
                 long_rows and self._use_sliced(dY.shape[1], S.n_src, S.n_dst, S.regular_t))):
             if S.split_t is None:

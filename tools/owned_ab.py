@@ -3,7 +3,7 @@ config 4's shapes in a loop of its own: pair and owned alternating (``sliced_own
 bit equality, then the sweep gate lag x rows per lane group.  ``python tools/owned_ab.py [OUT.json]``; with ``pmc`` as the
 first argument it only runs three calls of each form per product (lags from ``PMC_LAGS``, default -1; workgroups per CU
 from ``PMC_WGS``, default 1), for ``rocprofv3 --pmc`` / ``--kernel-trace`` runs of their own (profiles/owned_rows/,
-profiles/owned_wgs/).  The loops time both owned forms: one 16-wave workgroup per CU and two 12-wave ones."""
+profiles/owned_wgs/, profiles/owned_slices/).  The loops time both owned forms: one 16-wave workgroup per CU and two 12-wave ones."""
 import json, os, sys, statistics
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,10 +13,10 @@ dev = torch.device("cuda")
 F = 128
 rng = np.random.default_rng(0)
 
-def bip(n_dst, n_src, E):
+def bip(n_dst, n_src, E, n_slices=8):
     dst = torch.from_numpy(rng.integers(0, n_dst, E).astype(np.int32)).to(dev)
     src = torch.from_numpy(rng.integers(0, n_src, E).astype(np.int32)).to(dev)
-    sl = ops.SlicedCSR(dst, src, n_dst, n_src)
+    sl = ops.SlicedCSR(dst, src, n_dst, n_src, n_slices=n_slices)
     return sl, sl.indices, False
 
 def knn(n, k=64):
@@ -27,7 +27,10 @@ def knn(n, k=64):
     return sl, (sl.indices | (mult[sl.eid.long()] << ops.MULT_SHIFT)).contiguous(), True
 
 products = {"100k_src_to_50k": bip(50_000, 100_000, 10_000_000), "50k_src_to_100k": bip(100_000, 50_000, 10_000_000),
-            "knn_100k": knn(100_000), "knn_50k": knn(50_000)}
+            "knn_100k": knn(100_000), "knn_50k": knn(50_000),
+            # the layout dgmi_sliced_layout_slices gives the first product's class (profiles/owned_slices/): last, so that
+            # the graphs above stay the ones of the earlier visits
+            "100k_src_to_50k_16_slices": bip(50_000, 100_000, 10_000_000, n_slices=16)}
 
 def timed(sl, ids, id_mult, X, ds, out, n=30):
     for _ in range(5):

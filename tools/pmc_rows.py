@@ -6,7 +6,7 @@ for path in glob.glob(sys.argv[1] + "/**/*_counter_collection.csv", recursive=Tr
         n = r["Kernel_Name"]
         if "spmm" not in n and "reduce_planes" not in n:
             continue
-        key = (int(r["Dispatch_Id"]), n.split("(")[0].replace("void dgmi::(anonymous namespace)::", "")[:60])
+        key = (int(r["Dispatch_Id"]), n.replace("void ", "").replace("dgmi::(anonymous namespace)::", "").split("(")[0][:60])
         d.setdefault(key, {})[r["Counter_Name"]] = float(r["Counter_Value"])
 for (disp, name), c in sorted(d.items()):
     extra = ""
