@@ -54,6 +54,10 @@
 // the 16-wave form runs.  Nothing waits for the other workgroup of a CU.  Measured (profiles/owned_wgs/README.md): the
 // kernel is short of waves (12 instead of 16 per CU: +17-23 %), yet 512 free-running workgroups drift over more slices
 // than 256 and lose in L2 misses more than the waves return, so the built-in rule selects the second form for no class.
+//
+// A bf16 table (x_bytes == 2) takes the same form through the same launcher (spmm_owned_try) and the same plan with 8
+// columns per lane; its kernel — the 16-wave form without a gate — is dgmi_owned_bf16.hip, its classes are
+// owned_class_form's for x_bytes == 2.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -77,33 +81,6 @@ constexpr int64_t kOwnedMinRows = 32768;   // built-in rule: below, a workgroup 
 constexpr int kOwnedLag = -1;
 constexpr int kOwnedWideSlices = 16;       // the slice count of the one class whose layout is not the pair's (dgmi_sliced_layout_slices)
 constexpr int kOwnedAssumedCus = 256;      // workgroups the layout rule plans for where no device can be asked (MI355X)
-
-struct OwnedWork {  // task k of a workgroup, decoded (wave-uniform except lds_row / rows: per lane group)
-  int phase, task, slice, col_round;
-  int64_t row_base;  // the lane group's first destination row is row_base + lds_row
-  int lds_row, rows;
-};
-
-// Decoded once, when a wave reserves the task, and carried.  `k` past the last task: a task without rows.
-__device__ __forceinline__ OwnedWork owned_decode(const OwnedPlan& pl, int64_t wg, int T, int k, int grp) {
-  OwnedWork w;
-  if (k >= pl.phases * T) {  // wave-uniform
-    w.phase = pl.phases;
-    w.task = w.slice = w.col_round = w.lds_row = w.rows = 0;
-    w.row_base = 0;
-    return w;
-  }
-  w.phase = k / T;
-  w.task = k - w.phase * T;
-  const OwnedPhase ph = owned_phase(pl, w.phase);
-  w.slice = ph.slice;
-  w.col_round = ph.col_round;
-  const OwnedTask t = owned_task(pl, wg, ph.row_round, w.task, grp);
-  w.row_base = t.row0 - t.lds_row;
-  w.lds_row = t.lds_row;
-  w.rows = t.rows;
-  return w;
-}
 
 // VALS: 0 = unit edge values, 2 = multiplicities in the id words (dgmi_sliced.hip).  WAVES: waves of the workgroup, the
 // last one the toucher: kOwnedWaves (one workgroup per CU, 4 waves per SIMD) or kOwnedPairWaves (two co-resident
@@ -497,8 +474,23 @@ int device_cus() {
 // `pl`: the plan of one workgroup per CU, which names the class.  0 = the pair, 1 = one 16-wave workgroup per CU,
 // 2 = two 12-wave workgroups per CU.  No class takes 2: forced for all 8 products of the step it ran every one of them
 // 30-35 % slower than the pair (profiles/owned_wgs/README.md); it stays behind sliced_owned_wgs = 2.
-int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+// `x_bytes`: bytes per element of the gathered table.  The classes of a bf16 table (x_bytes == 2: dgmi_owned_bf16.hip;
+// column rounds of 8 lpr columns, table bytes in bf16) are classes of their own, measured on their own against the bf16
+// pair on the 8-slice layout (tools/bf16_owned_ab.py, profiles/owned_bf16/README.md).  All four classes of the eight
+// config-4 products cleared the bar — the owned median below the pair's by more than the pair's min .. max spread — with
+// -20 % to -30 % of the product, conversion pass included: every one is a single column round of 16-lane groups over
+// slices that fit an L2 at full width.
+int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes, int x_bytes) {
   const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (x_bytes == 2) {
+    if (pl.slices != kOwnedSlices || pl.col_rounds != 1) return 0;
+    if (pl.row_rounds == 1 && !id_mult && mib(16, 32)) return 1;  // 100 000 sources -> 50 000 rows, unit values
+    if (pl.row_rounds == 2 && !id_mult && mib(8, 16)) return 1;   // 50 000 sources -> 100 000 rows, unit values
+    if (pl.row_rounds == 2 && id_mult && mib(16, 32)) return 1;   // kNN-64 at 100 000 nodes
+    if (pl.row_rounds == 1 && id_mult && mib(8, 16)) return 1;    // kNN-64 at 50 000 nodes
+    return 0;
+  }
+  if (x_bytes != 4) return 0;
   if (pl.slices == kOwnedSlices) {
     if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return 1;
     if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return 1;
@@ -511,7 +503,8 @@ int owned_class_form(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
 // The built-in R's tasks-per-phase target of a class: kOwnedPhaseTasksMult for the two kNN-64 classes of the rule above,
 // which were measured with the hand-over (profiles/owned_carry/README.md: R = 3 instead of 4), kOwnedPhaseTasks for
 // every other product — also for ids with multiplicities of shapes nobody has measured.  (R does not enter the class.)
-int owned_class_phase_tasks(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+int owned_class_phase_tasks(const OwnedPlan& pl, bool id_mult, int64_t table_bytes, int x_bytes) {
+  if (x_bytes != 4) return kOwnedPhaseTasks;  // no bf16 class has been measured with another target
   const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
   if (pl.slices != kOwnedSlices) return kOwnedPhaseTasks;
   if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return kOwnedPhaseTasksMult;
@@ -585,9 +578,14 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   *taken = false;
   const Tuning& tune = tuning();
   if (tune.sliced_owned == 0) return hipSuccess;
-  if (a.x_bytes != 4 || a.vals != nullptr || a.src_scale != nullptr || a.n_keep != 0 || a.n_slices < 1 || a.n_slices > kOwnedMaxSlices ||
+  if ((a.x_bytes != 4 && a.x_bytes != 2) || a.vals != nullptr || a.src_scale != nullptr || a.n_keep != 0 || a.n_slices < 1 || a.n_slices > kOwnedMaxSlices ||
       tune.sliced_chunk_rows > 0 || a.chunk_rows < a.n_dst || a.n_dst == 0 || a.F == 0)
     return hipSuccess;
+  // Tuning::sliced_owned_slices is the knob of the fp32 layout experiment (dgmi_sliced_layout_slices, at the end): it
+  // names the slice count of the layouts made FOR the owned form.  No layout is ever made for it on behalf of a bf16
+  // product — the layout rule is fp32's, a bf16 product stays on the pair's 8-slice layout whatever the knob says — so a
+  // process that runs that experiment keeps what it ran for a bf16 table before this form took one: the pair.
+  if (a.x_bytes == 2 && tune.sliced_owned_slices > 0) return hipSuccess;
   // a forced grid counts workgroups, whichever form runs them
   const int64_t grid = tune.sliced_owned_grid > 0 ? tune.sliced_owned_grid : device_cus();
   if (grid < 1) return hipSuccess;
@@ -595,21 +593,29 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   // the one-workgroup plan names the class and is what a two-workgroup launch that cannot co-reside falls back to
   // the plan with the general tasks-per-phase target names the class; the two measured kNN-64 classes then take theirs
   const int slices = (int)a.n_slices;
-  OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, kOwnedPhaseTasks, slices);
-  const int phase_tasks = a.n_dst < kOwnedMinRows ? kOwnedPhaseTasks
-                                                   : owned_class_phase_tasks(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float));
+  const int cols = 16 / a.x_bytes;  // the columns of a lane's one 16-B load: 4 of an fp32 table, 8 of a bf16 one
+  const int64_t table_bytes = a.n_src * a.ldx * (int64_t)a.x_bytes;
+  OwnedPlan pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, kOwnedPhaseTasks, slices, cols);
+  const int phase_tasks = a.n_dst < kOwnedMinRows ? kOwnedPhaseTasks : owned_class_phase_tasks(pl, a.id_mult, table_bytes, a.x_bytes);
   if (pl.ok && phase_tasks != kOwnedPhaseTasks)
-    pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks, slices);
+    pl = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks, slices, cols);
   if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return hipSuccess;
+  const int rule = a.n_dst < kOwnedMinRows ? 0 : owned_class_form(pl, a.id_mult, table_bytes, a.x_bytes);
+  if (tune.sliced_owned != 1 && rule == 0) return hipSuccess;
+  const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * a.x_bytes < ((int64_t)1 << 32);
+  if (a.x_bytes == 2) {
+    // The bf16 kernel (dgmi_owned_bf16.hip) is built in one form only — one 16-wave workgroup per CU, no phase gate —
+    // so sliced_owned_lag, sliced_owned_spin_ticks and sliced_owned_wgs are ignored for a bf16 table, and without
+    // arrive counters nothing is asked of the plane workspace.
+    *taken = true;
+    return launch_owned_bf16(a, pl, lpr, grid, off32, s);
+  }
   // the arrive counters live in the first bytes of the caller's plane workspace (n_slices * n_dst * ldp floats)
   const auto arrive_fits = [&](const OwnedPlan& p) {
     return sizeof(unsigned) * 8 * (size_t)p.phases <= sizeof(float) * (size_t)a.n_slices * (size_t)a.n_dst * (size_t)a.ldp;
   };
   if (!arrive_fits(pl)) return hipSuccess;
-  const int rule = a.n_dst < kOwnedMinRows ? 0 : owned_class_form(pl, a.id_mult, a.n_src * a.ldx * (int64_t)sizeof(float));
-  if (tune.sliced_owned != 1 && rule == 0) return hipSuccess;
   const int form = tune.sliced_owned_wgs == 1 || tune.sliced_owned_wgs == 2 ? tune.sliced_owned_wgs : (rule == 2 ? 2 : 1);
-  const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * 4 < ((int64_t)1 << 32);
   const int64_t spin = tune.sliced_owned_spin_ticks > 0 ? tune.sliced_owned_spin_ticks : kOwnedSpinTicks;
   const int lag = tune.sliced_owned_lag >= -1 ? tune.sliced_owned_lag : kOwnedLag;
   *taken = true;
@@ -655,7 +661,7 @@ int sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, bool id_mult) 
   if (!pl.ok || pl.lds_bytes > (size_t)(160 << 10)) return kOwnedSlices;
   if (forced > 0) return slices;
   if (n_dst < kOwnedMinRows) return kOwnedSlices;
-  return owned_class_form(pl, id_mult, n_src * F * (int64_t)sizeof(float)) == 1 ? slices : kOwnedSlices;
+  return owned_class_form(pl, id_mult, n_src * F * (int64_t)sizeof(float), 4) == 1 ? slices : kOwnedSlices;
 }
 
 }  // namespace dgmi

@@ -5,7 +5,7 @@
 // hand-over from task to task (owned_carry_*).
 //
 // Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
-// column tile (16 LPR bytes) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
+// column tile (16 LPR bytes; 32 LPR where a lane owns 8 columns, dgmi_owned_bf16.hip) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
 // (column round, row round, slice), slices 0 .. S - 1 innermost and in order: the row sums take their S segment sums in
 // the order the plane reduce adds the planes.  S is the layout's slice count, a field of the plan (8 unless the caller
 // says otherwise): nothing binds a workgroup to an XCD, so the form walks as many slices as the layout has.  A phase is cut into TASKS of G R consecutive rows of the round — one wave,
@@ -58,25 +58,27 @@ struct OwnedTask {
 // (forces row rounds); `wgs_per_cu`: 1 = one 16-wave workgroup per CU, 2 = two co-resident 12-wave workgroups, each with
 // half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way);
 // `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes);
-// `slices`: the slice count of the layout, 1 .. kOwnedMaxSlices.
+// `slices`: the slice count of the layout, 1 .. kOwnedMaxSlices; `cols_per_lane`: the columns a lane owns — 4 of an fp32
+// table, 8 of a bf16 one (dgmi_owned_bf16.hip): a column round is cols_per_lane lpr columns wide, and a row of it costs
+// 4 cols_per_lane lpr bytes of LDS (the sums are fp32 either way).
 __host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
 
 __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap,
                                                 int wgs_per_cu = 1, int phase_tasks_target = kOwnedPhaseTasks,
-                                                int slices = kOwnedSlices) {
+                                                int slices = kOwnedSlices, int cols_per_lane = 4) {
   OwnedPlan p{};
   p.ok = false;
   p.n_dst = n_dst;
   if (n_dst < 1 || F < 1 || grid < 1 || (wgs_per_cu != 1 && wgs_per_cu != 2) || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64) ||
-      slices < 1 || slices > kOwnedMaxSlices)
+      slices < 1 || slices > kOwnedMaxSlices || (cols_per_lane != 4 && cols_per_lane != 8))
     return p;
   p.lpr = lpr;
   p.slices = slices;
   p.G = 64 / lpr;
-  p.col_rounds = (int)((F + 4 * lpr - 1) / (4 * lpr));
+  p.col_rounds = (int)((F + cols_per_lane * lpr - 1) / (cols_per_lane * lpr));
   p.wg_rows = (n_dst + grid - 1) / grid;
   p.active = (n_dst + p.wg_rows - 1) / p.wg_rows;
-  int64_t fit = kOwnedLdsRowBytes / wgs_per_cu / (16 * lpr);
+  int64_t fit = kOwnedLdsRowBytes / wgs_per_cu / (4 * cols_per_lane * lpr);
   if (lds_rows_cap > 0 && lds_rows_cap < fit) fit = lds_rows_cap;
   const int64_t rounds = (p.wg_rows + fit - 1) / fit;
   if (rounds * p.col_rounds * slices > kOwnedMaxPhases) return p;
@@ -94,7 +96,7 @@ __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lp
   if (R < 1) R = 1;
   p.R = R;
   p.tasks = (p.round_rows + p.G * R - 1) / (p.G * R);
-  p.lds_bytes = (size_t)p.round_rows * 16 * lpr + sizeof(int) * ((size_t)p.tasks + p.phases + 2);
+  p.lds_bytes = (size_t)p.round_rows * 4 * cols_per_lane * lpr + sizeof(int) * ((size_t)p.tasks + p.phases + 2);
   p.ok = true;
   return p;
 }
@@ -130,6 +132,35 @@ __host__ __device__ inline OwnedTask owned_task(const OwnedPlan& p, int64_t wg, 
   int64_t rows = owned_round_rows(p, wg, row_round) - lds_row;
   rows = rows < 0 ? 0 : (rows < p.R ? rows : p.R);
   return OwnedTask{wg * p.wg_rows + (int64_t)row_round * p.round_rows + lds_row, (int)lds_row, (int)rows};
+}
+
+// Task k of a workgroup (T task slots per phase, phase-major), decoded for lane group `grp`: wave-uniform except
+// lds_row / rows, which are the lane group's.  `k` past the last task: a task without rows.  A kernel decodes a task
+// once, when a wave reserves it, and carries it.
+struct OwnedWork {
+  int phase, task, slice, col_round;
+  int64_t row_base;  // the lane group's first destination row is row_base + lds_row
+  int lds_row, rows;
+};
+
+__host__ __device__ __forceinline__ OwnedWork owned_decode(const OwnedPlan& pl, int64_t wg, int T, int k, int grp) {
+  OwnedWork w;
+  if (k >= pl.phases * T) {  // wave-uniform
+    w.phase = pl.phases;
+    w.task = w.slice = w.col_round = w.lds_row = w.rows = 0;
+    w.row_base = 0;
+    return w;
+  }
+  w.phase = k / T;
+  w.task = k - w.phase * T;
+  const OwnedPhase ph = owned_phase(pl, w.phase);
+  w.slice = ph.slice;
+  w.col_round = ph.col_round;
+  const OwnedTask t = owned_task(pl, wg, ph.row_round, w.task, grp);
+  w.row_base = t.row0 - t.lds_row;
+  w.lds_row = t.lds_row;
+  w.rows = t.rows;
+  return w;
 }
 
 // The rolling gather window.  A lane group sums the L edges of its run (all the rows of its task, in order) with

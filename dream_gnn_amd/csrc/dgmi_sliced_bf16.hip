@@ -22,7 +22,6 @@ namespace {
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // two fp32 -> one dword of two bf16, round-to-nearest-even (v_cvt_pk_bf16_f32); element 0 in the low half
 __device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
@@ -53,20 +52,8 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restri
   }
 }
 
-// Source row `idx` of the bf16 table: this lane's 8 columns, one 16-B load.  OFF32: the table is < 4 GiB (see ld_row of
-// dgmi_sliced_common.h).
-template <bool OFF32>
-__device__ __forceinline__ v4u ld_row8(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Xc, int idx, int64_t ldx,
-                                       uint32_t row_bytes, uint32_t col_bytes) {
-  if (OFF32) return *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
-  return *reinterpret_cast<const v4u*>(Xc + (int64_t)idx * ldx);
-}
-
-// bf16 -> fp32 is a shift (element 2k: the low half of dword k) or a mask (element 2k + 1): exact
-__device__ __forceinline__ float4 widen(uint32_t u0, uint32_t u1) {
-  return make_float4(__uint_as_float(u0 << 16), __uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 << 16),
-                     __uint_as_float(u1 & 0xffff0000u));
-}
+// The 16-B load of a lane's 8 columns and the exact widening (ld_row8, widen): dgmi_sliced_common.h — the workgroup-owned
+// form (dgmi_owned_bf16.hip) gathers with them too.
 
 // One dword (2 columns) of a fast-path batch: widen, and the canonical in-order sum of spmm_sliced_vec4_kernel
 // (acc = fmaf(w, x, acc) or acc + x, edge by edge) on each of the two columns.
@@ -277,6 +264,9 @@ hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t
 // bf16 slice: sliced_lpr (dgmi_sliced_common.h).
 hipError_t spmm_sliced_bf16(const SlicedArgs& a, hipStream_t s) {
   if (a.x_bytes != 2 || a.src_scale != nullptr) return hipErrorInvalidValue;  // the source scale belongs to rows_to_bf16
+  bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip, dgmi_owned_bf16.hip)
+  const hipError_t err = spmm_owned_try(a, s, &owned);
+  if (err != hipSuccess || owned) return err;
   return spmm_sliced_chunks(a, launch_gather_bf16, s);
 }
 

@@ -23,6 +23,11 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStrea
 // product was launched; false (and hipSuccess): the form does not take it and the caller runs the pair.
 hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken);
 
+// The same form gathering from a bf16 table (dgmi_owned_bf16.hip): the launch of a product spmm_owned_try has planned
+// with 8 columns per lane (`pl`), at lane-group width 8 / 16 / 32, on `grid` workgroups of kOwnedWaves waves.
+struct OwnedPlan;
+hipError_t launch_owned_bf16(const SlicedArgs& a, const OwnedPlan& pl, int lpr, int64_t grid, bool off32, hipStream_t s);
+
 namespace {
 
 constexpr int64_t kColumnPassMinRows = 32768;  // column passes only when a pass still has >= ~8k waves
@@ -50,6 +55,22 @@ __device__ __forceinline__ float4 ld_row(const float* __restrict__ X, const floa
   // X is the (wave-uniform) table base, Xc = X + this lane's column
   if (OFF32) return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
   return ld4(Xc + (int64_t)idx * ldx);
+}
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// Source row `idx` of the bf16 table: this lane's 8 columns, one 16-B load.  OFF32: the table is < 4 GiB (see ld_row).
+template <bool OFF32>
+__device__ __forceinline__ v4u ld_row8(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Xc, int idx, int64_t ldx,
+                                       uint32_t row_bytes, uint32_t col_bytes) {
+  if (OFF32) return *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
+  return *reinterpret_cast<const v4u*>(Xc + (int64_t)idx * ldx);
+}
+
+// bf16 -> fp32 is a shift (element 2k: the low half of dword k) or a mask (element 2k + 1): exact
+__device__ __forceinline__ float4 widen(uint32_t u0, uint32_t u1) {
+  return make_float4(__uint_as_float(u0 << 16), __uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 << 16),
+                     __uint_as_float(u1 & 0xffff0000u));
 }
 
 // Which destination rows a lane group sums.  A chunk's rows [0, n_rows) (relative to row_begin) are cut, in order, into

@@ -893,7 +893,7 @@ class CSRGraph:
         """The plain XCD-local product with a bf16 gather: ``gathered_scale`` multiplies the gathered rows (folded into
         the conversion of a float32 ``X``), ``out_scale`` the output rows (applied by the plane reduce)."""
         S = self._S
-        name, layout = self._layout_of(transposed)  # the pair's 8 slices: the owned form gathers no bf16
+        name, layout = self._layout_of(transposed)  # the pair's 8 slices: the library runs its owned form on them where it wins (DESIGN §4.12)
         mult = self._mult_ids(name, layout)
         if mult is not None:  # the scale of `scale x multiplicity` values lands on the output rows or on the gathered rows
             if (mult[0] == "row") != transposed:
@@ -925,8 +925,9 @@ class CSRGraph:
         unless the product is of the class the workgroup-owned form runs faster on 16, or ``sliced_owned_slices``
         forces a count).  Only a product that form can take is asked about: unit values or multiplicities in the id
         words, no edge dropout evaluated inside the kernel (a compacted view runs the plain kernels), and a scale on
-        the gathered rows only where the pre-scale pass takes it out of the kernel.  Every other product — and the bf16
-        gather — runs the pair on the 8-slice layout, as does every shape the library answers 8 for.  Which layout a
+        the gathered rows only where the pre-scale pass takes it out of the kernel.  Every other product runs the pair on
+        the 8-slice layout; the bf16 gather stays on that layout too (there the library runs its owned form for the
+        measured bf16 classes), as does every shape the library answers 8 for.  Which layout a
         product runs on depends on the product alone, never on what the graph has built before (:meth:`_layout_of`)."""
         S = self._S
         n_rows, n_cols = (S.n_src, S.n_dst) if transposed else (S.n_dst, S.n_src)

@@ -43,7 +43,9 @@ DGMI_API int dgmi_rows_to_bf16(const float* X, int64_t ldx, const float* scale, 
  * The argument list is that of dgmi_spmm_sliced_f32 without src_scale (it belongs to dgmi_rows_to_bf16): X holds
  * n_src rows of F bf16 values with leading dimension ldx (elements); every other argument — vals, eid / keep / n_keep
  * (edge dropout on the fly), dst_scale, column_passes, id_multiplicity, the epilogue — means what it means there.
- * `planes` is fp32 scratch of dgmi_spmm_sliced_planes_bytes(n_dst, n_slices, F) bytes, as for the fp32 product.
+ * `planes` is fp32 scratch of dgmi_spmm_sliced_planes_bytes(n_dst, n_slices, F) bytes, as for the fp32 product.  It is
+ * always required, but may go unused: a product the library runs in its workgroup-owned form (rows summed in LDS, one
+ * launch; the same bits) writes no planes.
  *
  * DGMI_ERR_INVALID_ARG (never a fault) unless F % 8 == 0, ldx >= F, ldx % 8 == 0, ldy >= F, ldy % 4 == 0 and X, Y and
  * planes are 16-byte aligned; and for everything dgmi_spmm_sliced_f32 refuses.  DGMI_ERR_WORKSPACE for short planes.
