@@ -1,15 +1,17 @@
 // dgmi_owned_common.h — the plan of the workgroup-owned form of the XCD-local SpMM (dgmi_owned.hip): which destination
 // rows a workgroup owns, how they are cut into rounds that fit its LDS, and which rows a task of a phase sums.  The
-// kernel, its launcher and the host test (tests/test_owned_plan_host.py) use owned_plan / owned_phase / owned_task and
-// nothing else.  At the end: the index arithmetic of the kernel's rolling gather window (owned_window_*) and of its
+// kernel body (dgmi_owned_kernel.h), its launcher and the host tests (tests/test_owned_*_host.py) take the plan from
+// owned_plan, a task from owned_decode (owned_phase / owned_task) and a workgroup's extents from owned_wg_tasks /
+// owned_round_rows.  At the end: the index arithmetic of the kernel's rolling gather window (owned_window_*) and of its
 // hand-over from task to task (owned_carry_*).
 //
 // Workgroup w owns the contiguous rows [w B, (w + 1) B), B = ceil(n_dst / grid).  LDS holds one fp32 partial row of one
-// column tile (16 LPR bytes; 32 LPR where a lane owns 8 columns, dgmi_owned_bf16.hip) per owned row of the current ROW ROUND; the column tiles are the COLUMN ROUNDS.  A PHASE is
-// (column round, row round, slice), slices 0 .. S - 1 innermost and in order: the row sums take their S segment sums in
-// the order the plane reduce adds the planes.  S is the layout's slice count, a field of the plan (8 unless the caller
-// says otherwise): nothing binds a workgroup to an XCD, so the form walks as many slices as the layout has.  A phase is cut into TASKS of G R consecutive rows of the round — one wave,
-// R rows for each of its G = 64 / LPR lane groups; task t of every phase of a round covers the same LDS rows.
+// column tile (16 LPR bytes; 32 LPR where a lane owns 8 columns: a bf16 table) per owned row of the current ROW ROUND;
+// the column tiles are the COLUMN ROUNDS.  A PHASE is (column round, row round, slice), slices 0 .. S - 1 innermost and
+// in order: the row sums take their S segment sums in the order the plane reduce adds the planes.  S is the layout's
+// slice count, a field of the plan (8 unless the caller says otherwise): nothing binds a workgroup to an XCD, so the
+// form walks as many slices as the layout has.  A phase is cut into TASKS of G R consecutive rows of the round — one
+// wave, R rows for each of its G = 64 / LPR lane groups; task t of every phase of a round covers the same LDS rows.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -59,7 +61,7 @@ struct OwnedTask {
 // half the LDS rows and a tasks-per-phase target scaled to its 11 workers (`grid` counts workgroups either way);
 // `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes);
 // `slices`: the slice count of the layout, 1 .. kOwnedMaxSlices; `cols_per_lane`: the columns a lane owns — 4 of an fp32
-// table, 8 of a bf16 one (dgmi_owned_bf16.hip): a column round is cols_per_lane lpr columns wide, and a row of it costs
+// table, 8 of a bf16 one (OwnedRowBf16, dgmi_owned_kernel.h): a column round is cols_per_lane lpr columns wide, and a row of it costs
 // 4 cols_per_lane lpr bytes of LDS (the sums are fp32 either way).
 __host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
 

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restri
 }
 
 // The 16-B load of a lane's 8 columns and the exact widening (ld_row8, widen): dgmi_sliced_common.h — the workgroup-owned
-// form (dgmi_owned_bf16.hip) gathers with them too.
+// form (OwnedRowBf16, dgmi_owned_kernel.h) gathers with them too.
 
 // One dword (2 columns) of a fast-path batch: widen, and the canonical in-order sum of spmm_sliced_vec4_kernel
 // (acc = fmaf(w, x, acc) or acc + x, edge by edge) on each of the two columns.
@@ -264,7 +264,7 @@ hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t
 // bf16 slice: sliced_lpr (dgmi_sliced_common.h).
 hipError_t spmm_sliced_bf16(const SlicedArgs& a, hipStream_t s) {
   if (a.x_bytes != 2 || a.src_scale != nullptr) return hipErrorInvalidValue;  // the source scale belongs to rows_to_bf16
-  bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip, dgmi_owned_bf16.hip)
+  bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip)
   const hipError_t err = spmm_owned_try(a, s, &owned);
   if (err != hipSuccess || owned) return err;
   return spmm_sliced_chunks(a, launch_gather_bf16, s);

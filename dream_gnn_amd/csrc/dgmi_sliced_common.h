@@ -19,14 +19,10 @@ typedef hipError_t (*SlicedGather)(const SlicedArgs& a, int lpr, int64_t row_beg
 // (sliced_lpr below), runs `gather` and then the plane reduce with the chunk's dst_scale / Y / mask offsets.
 hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStream_t s);
 
-// The workgroup-owned form (dgmi_owned.hip): rows summed in LDS, no planes, bit-identical to the pair.  *taken: the
-// product was launched; false (and hipSuccess): the form does not take it and the caller runs the pair.
+// The workgroup-owned form (dgmi_owned.hip): rows summed in LDS, no planes, bit-identical to the pair, from an fp32 or
+// a bf16 table.  *taken: the product was launched; false (and hipSuccess): the form does not take it and the caller
+// runs the pair.
 hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken);
-
-// The same form gathering from a bf16 table (dgmi_owned_bf16.hip): the launch of a product spmm_owned_try has planned
-// with 8 columns per lane (`pl`), at lane-group width 8 / 16 / 32, on `grid` workgroups of kOwnedWaves waves.
-struct OwnedPlan;
-hipError_t launch_owned_bf16(const SlicedArgs& a, const OwnedPlan& pl, int lpr, int64_t grid, bool off32, hipStream_t s);
 
 namespace {
 

@@ -1,4 +1,4 @@
-"""The hand-over of the gather window from task to task in the workgroup-owned SpMM (csrc/dgmi_owned.hip; its index
+"""The hand-over of the gather window from task to task in the workgroup-owned SpMM (csrc/dgmi_owned_kernel.h; its index
 arithmetic: ``owned_carry_*`` in csrc/dgmi_owned_common.h) on the graph designed for the window itself
 (_owned_window_cases.py), with the order in which one wave runs the tasks of a workgroup restated on the host.  Plain
 module, shared by test_owned_carry_host.py — which proves that every kind of consecutive pair of runs occurs under the

@@ -1,4 +1,4 @@
-"""A graph designed for the rolling gather window of the workgroup-owned SpMM (csrc/dgmi_owned.hip; the window's index
+"""A graph designed for the rolling gather window of the workgroup-owned SpMM (csrc/dgmi_owned_kernel.h; the window's index
 arithmetic: csrc/dgmi_owned_common.h), and the plan of the forced form restated on the host.  Plain module (like
 _spmm_cases.py), shared by test_owned_window_host.py — which checks that the design covers what it claims, for every
 setting the GPU test runs — and test_gpu_spmm_owned_window.py.

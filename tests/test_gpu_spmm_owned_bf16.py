@@ -1,4 +1,4 @@
-"""The workgroup-owned form of the XCD-local SpMM gathering from a bf16 table (csrc/dgmi_owned_bf16.hip: rows summed in
+"""The workgroup-owned form of the XCD-local SpMM gathering from a bf16 table (csrc/dgmi_owned.hip: rows summed in
 LDS, 8 columns per lane, no partial planes), forced with ``sliced_owned = 1`` through ``dgmi_spmm_sliced_bf16``, so that
 ``Y`` may be strided.  On the designed integer operands of _spmm_cases.py (exact in bf16, sums exact in fp32) it is held
 to ZERO tolerance (``torch.equal``) under every knob that shapes its plan; on ``randn`` tables rounded by
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import _owned_window_cases as D
 import _spmm_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -203,6 +204,41 @@ def test_owned_bf16_exact_on_designed_operands(dev, kind, F):
                          ld_y=F + 8 if i % 2 else None)
             assert torch.equal(y, want[has_ds, epi]), "%s dst_scale=%s epilogue=%s: %d elements differ, first row %d" % (
                 knobs, has_ds, epi, int((y != want[has_ds, epi]).sum()), int((y != want[has_ds, epi]).any(1).nonzero()[0]))
+
+
+def _stage_window(dev):
+    from dream_gnn_amd import ops
+
+    if "window" not in _staged:
+        d = D.design()
+        sl = ops.SlicedCSR(_t(d.dst, dev), _t(d.src, dev), d.n_dst, d.n_src, n_slices=D.N_SLICES)
+        assert np.array_equal(sl.segptr.cpu().numpy(), d.segptr) and np.array_equal(sl.indices.cpu().numpy(), d.indices)
+        ids = (sl.indices | ((_t(d.mult, dev) - 1)[sl.eid.long()] << ops.MULT_SHIFT)).contiguous()
+        _staged["window"] = dict(d=d, sl=sl, ids=ids)
+    return _staged["window"]
+
+
+@pytest.mark.parametrize("F", [8, 128, 344])
+@pytest.mark.parametrize("kind", ["unit", "mult"])
+def test_owned_bf16_window_exact_on_the_designed_graph(dev, kind, F):
+    """The graph designed for the rolling window (_owned_window_cases.py: every segment length around the window and
+    the lane-group widths as first, middle and last row of a run, empty tasks, a last id of ``n_src - 1``), which
+    test_gpu_spmm_owned_window.py runs through the fp32 kernel: the group, last-group and drain paths are those of the
+    one kernel body, here under the bf16 row policy.  Its settings at the widths a bf16 table has."""
+    st = _stage_window(dev)
+    d, sl = st["d"], st["sl"]
+    X = np.random.default_rng(7 * F + 1).integers(-8, 9, (d.n_src, F)).astype(np.float32)
+    want = _t(D.reference(d, X, d.mult if kind == "mult" else None), dev)
+    ids = st["ids"] if kind == "mult" else sl.indices
+    Xb = _t(X, dev).to(BF16)
+    assert torch.equal(Xb.float(), _t(X, dev))  # integers in [-8, 8] are exact in bf16
+    settings = [knobs for knobs in D.settings() if knobs["sliced_lpr"] in WIDTHS]
+    assert len(settings) == len(D.settings()) * 3 // 4
+    for i, knobs in enumerate(settings):
+        _set(sliced_owned=1, **knobs)
+        y = _product(sl, ids, kind == "mult", Xb, ld_y=F + 8 if i % 2 == 0 else None)  # (_product checks the NaN frame)
+        assert torch.equal(y, want), "%s: %d elements differ, first row %d" % (
+            knobs, int((y != want).sum()), int((y != want).any(1).nonzero()[0]))
 
 
 # ---------------------------------------------------------------------------------------------

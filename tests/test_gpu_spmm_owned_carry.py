@@ -1,4 +1,4 @@
-"""The hand-over of the gather window from task to task in the workgroup-owned SpMM (csrc/dgmi_owned.hip) on the designed
+"""The hand-over of the gather window from task to task in the workgroup-owned SpMM (csrc/dgmi_owned_kernel.h) on the designed
 graph of _owned_window_cases.py, whose consecutive pairs of runs _owned_carry_cases.py restates
 (test_owned_carry_host.py shows which kinds of pair occur under the settings used here).
 

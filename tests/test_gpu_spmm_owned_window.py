@@ -1,4 +1,4 @@
-"""The rolling gather window of the workgroup-owned SpMM (csrc/dgmi_owned.hip) on the graph designed for it
+"""The rolling gather window of the workgroup-owned SpMM (csrc/dgmi_owned_kernel.h) on the graph designed for it
 (_owned_window_cases.py: every segment length around the window and the lane-group widths, in every slice, as first,
 middle and last row of a run; runs shorter than the window, exact multiples, runs ending in empty rows, empty tasks, a
 last source id of ``n_src - 1``; test_owned_window_host.py checks that it covers all that under every setting used here).

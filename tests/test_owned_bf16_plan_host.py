@@ -1,5 +1,5 @@
 """The plan of the workgroup-owned SpMM with EIGHT columns per lane (``owned_plan(..., cols_per_lane = 8)``,
-csrc/dgmi_owned_common.h: the bf16 gather of csrc/dgmi_owned_bf16.hip) on the host (no GPU): a stand-alone C++ program
+csrc/dgmi_owned_common.h: the bf16 gather of csrc/dgmi_owned.hip) on the host (no GPU): a stand-alone C++ program
 includes the header the kernel and its launcher include and walks every workgroup, phase, task slot and lane group.
 Every (row, slice, 8 lpr-column tile) must be covered exactly once; a task slot covers the same rows in every phase of a
 round; ``lds_bytes`` is ``round_rows * 32 lpr`` plus the control words and stays inside the CU's 160 KiB; at most 128

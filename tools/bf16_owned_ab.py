@@ -1,4 +1,4 @@
-"""The workgroup-owned bf16 gather (csrc/dgmi_owned_bf16.hip) against the bf16 pair of launches, on the eight config-4
+"""The workgroup-owned bf16 gather (``spmm_owned_bf16_kernel``, csrc/dgmi_owned.hip) against the bf16 pair of launches, on the eight config-4
 products of bench.py — the A/B the built-in rule's bf16 classes are decided by (profiles/owned_bf16/README.md).
 
     python tools/bf16_owned_ab.py [--reps 20] [--rounds 7] [--variants pair,owned,rule] [--out profiles/owned_bf16/ab.json]
