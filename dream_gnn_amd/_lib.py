@@ -119,6 +119,14 @@ GIVEN_SIGNATURES = {
                                                    ctypes.c_size_t, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/dgmi_curve.h (its own table, for the same reason).
+CURVE_SIGNATURES = {
+    "dgmi_curve_areas_workspace_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "dgmi_curve_areas_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                            _vp]),
+}
+CURVE_MAX_SEGMENTS = 1 << 24  # DGMI_CURVE_MAX_SEGMENTS
+
 # name -> (restype, argtypes); mirrors include/dgmi_layout.h (a seventh table, for the same reason).
 LAYOUT_SIGNATURES = {
     "dgmi_sliced_layout_slices": (ctypes.c_int32, [_i64, _i64, _i64, ctypes.c_int32]),
@@ -137,8 +145,9 @@ def _load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
                               + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
-                              + list(GIVEN_SIGNATURES.items()) + list(LAYOUT_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the seven headers declare
+                              + list(GIVEN_SIGNATURES.items()) + list(CURVE_SIGNATURES.items())
+                              + list(LAYOUT_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the eight headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

@@ -27,6 +27,7 @@
 #include "dgmi.h"
 #include "dgmi_above.h"
 #include "dgmi_bf16.h"
+#include "dgmi_curve.h"
 #include "dgmi_given.h"
 #include "dgmi_pairs.h"
 #include "dgmi_rank.h"
@@ -648,6 +649,56 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_rank_list(const Tensor& X, c
   return {o.logit, o.above, o.total, o.info};
 }
 
+// exact AUROC / AUPR of scored samples, overall (n_segments = 0) or per segment (dgmi_curve.hip): count = (S, 6) int64
+// rows (P, N, TP at the threshold, FP at the threshold, groups, U2), area = (S, 2) float64 rows (auroc, aupr), info =
+// [flag word] (bit 0 NaN score, bit 1 label not 0 / 1, bit 2 segment id out of range).  Any shape of score (flattened);
+// labels of bool / integer dtype become fp32, segments int32; the inputs are not modified.  The workspace comes from
+// the caching allocator per call, as pair_mlp_topk; nothing synchronises.  Not differentiable.
+std::tuple<Tensor, Tensor, Tensor> curve_areas(const Tensor& score, const Tensor& label, const OptTensor& segment,
+                                               int64_t n_segments, double threshold) {
+  check_dev(score, "score");
+  check_dev(label, "label");
+  TORCH_CHECK(score.scalar_type() == at::kFloat, "score must be float32, got ", c10::toString(score.scalar_type()));
+  TORCH_CHECK(label.device() == score.device(), "tensors on different devices: label on ", label.device().str(), " vs ",
+              score.device().str());
+  const auto lt = label.scalar_type();
+  TORCH_CHECK(lt == at::kFloat || lt == at::kBool || c10::isIntegralType(lt, false), "label must be float32, bool or an integer dtype, got ",
+              c10::toString(lt));
+  TORCH_CHECK(n_segments >= 0 && n_segments <= DGMI_CURVE_MAX_SEGMENTS, "n_segments must be in 0..", DGMI_CURVE_MAX_SEGMENTS,
+              ", got ", n_segments);
+  const bool has_seg = segment.has_value() && segment->defined();
+  TORCH_CHECK(has_seg == (n_segments > 0), "segment ids and n_segments > 0 go together");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(score.device());
+  Tensor sc = score.reshape({-1}).contiguous();
+  Tensor lb = label.reshape({-1}).to(at::kFloat).contiguous();
+  const int64_t n = sc.numel();
+  TORCH_CHECK(lb.numel() == n, "score has ", n, " entries, label has ", lb.numel());
+  TORCH_CHECK(n <= (int64_t)INT32_MAX, "at most 2^31 - 1 samples, got ", n);
+  Tensor sg;
+  if (has_seg) {
+    check_dev(*segment, "segment");
+    const auto st = segment->scalar_type();
+    TORCH_CHECK((st == at::kInt || st == at::kLong) && segment->device() == score.device(),
+                "segment must be an int32 / int64 tensor on ", score.device().str());
+    Tensor flat = segment->reshape({-1});
+    TORCH_CHECK(flat.numel() == n, "score has ", n, " entries, segment has ", flat.numel());
+    sg = st == at::kInt ? flat.contiguous() : flat.clamp(-1, (int64_t)INT32_MAX).to(at::kInt).contiguous();
+  }
+  const int64_t S = n_segments > 0 ? n_segments : 1;
+  auto opts = sc.options();
+  Tensor count = at::empty({S, 6}, opts.dtype(at::kLong)), area = at::empty({S, 2}, opts.dtype(at::kDouble));
+  Tensor info = at::empty({1}, opts.dtype(at::kInt));
+  const size_t wbytes = dgmi_curve_areas_workspace_bytes(n, n_segments);
+  Tensor ws = at::empty({(int64_t)(wbytes < 16 ? 16 : wbytes)}, opts.dtype(at::kByte));
+  check_status(dgmi_curve_areas_f32(n ? sc.data_ptr<float>() : nullptr, n ? lb.data_ptr<float>() : nullptr,
+                                    // an empty tensor has no storage; with n = 0 no id is read, any non-null pointer does
+                                    has_seg ? (n ? sg.data_ptr<int32_t>() : reinterpret_cast<const int32_t*>(ws.data_ptr())) : nullptr,
+                                    n, n_segments, (float)threshold, count.data_ptr<int64_t>(), area.data_ptr<double>(),
+                                    info.data_ptr<int32_t>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(sc)),
+               "dgmi_curve_areas_f32");
+  return {count, area, info};
+}
+
 // every novel pair whose decoder logit reaches `min_logit` (dgmi_pairs_above.hip), appended in scheduling order to the
 // caller's record tensors (capacity = their length; 0 = count only): returns count = [the exact int64 number of
 // qualifying pairs, which may exceed the capacity] and info = [0, out-of-range flag].  Nothing is written past the
@@ -1054,3 +1105,11 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(dreamgnn_mi, Autograd, m) { m.impl("spmm_csr", spmm_csr_autograd); }
+
+// The evaluation metrics, registered as a fragment of their own: curve_areas reads scores and writes statistics, it
+// is no operand of a product, so its operand forms are tested with its arithmetic (tests/test_gpu_curve.py) and not in
+// the binding case table, which holds one case per op of the block above (tests/_binding_cases.py).
+TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, metrics) {
+  metrics.def("curve_areas(Tensor score, Tensor label, Tensor? segment, int n_segments, float threshold) -> (Tensor count, Tensor area, Tensor info)");
+}
+TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, metrics) { metrics.impl("curve_areas", curve_areas); }

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import graph as G
+from . import ops
 from .model import common_loss
 
 
@@ -173,3 +174,29 @@ def evaluate(net, batch: Dict, labels: torch.Tensor):
                    batch["drug_feat"], batch["disease_graph"], batch["disease_sim_feat"], batch["disease_feat"],
                    batch.get("drug_feature_graph"), batch.get("disease_feature_graph"))
     return auroc_aupr(labels.cpu().numpy(), pred.view(-1).cpu().numpy())
+
+
+def auroc_aupr_device(y_true: torch.Tensor, y_score: torch.Tensor, segment: Optional[torch.Tensor] = None,
+                      n_segments: int = 0, check: bool = False) -> "ops.CurveStats":
+    """:func:`auroc_aupr` on the device (``ops.curve_areas``): exact, no host transfer, and per segment when asked."""
+    return ops.curve_areas(y_score, y_true, segment, n_segments, check=check)
+
+
+@torch.no_grad()
+def evaluate_device(net, batch: Dict, labels: torch.Tensor, by: Optional[str] = None, check: bool = False) -> "ops.CurveStats":
+    """:func:`evaluate` with the metrics computed on the device: the same eval-mode forward, then ``ops.curve_areas``
+    on the logits — no device-to-host copy, no host sort, nothing read back with ``check=False``.  This is the way to
+    evaluate between replays of :class:`CapturedTrainStep` (the reference evaluates every 250 iterations,
+    train.py:303-323).  ``by="disease"`` / ``by="drug"`` segments the samples by the decoder graph's ids: one
+    AUROC / AUPR per disease / per drug (``CurveStats.macro()`` averages them)."""
+    if by not in (None, "disease", "drug"):
+        raise ValueError("by must be None, 'disease' or 'drug', got %r" % (by,))
+    net.eval()
+    pred, *_ = net(batch["enc_graph"], batch["dec_graph"], batch["drug_graph"], batch["drug_sim_feat"],
+                   batch["drug_feat"], batch["disease_graph"], batch["disease_sim_feat"], batch["disease_feat"],
+                   batch.get("drug_feature_graph"), batch.get("disease_feature_graph"))
+    if by is None:
+        return ops.curve_areas(pred.view(-1), labels, check=check)
+    pairs = batch["dec_graph"].edge_pairs()
+    ids, n = (pairs.dst, pairs.n_dst) if by == "disease" else (pairs.src, pairs.n_src)
+    return ops.curve_areas(pred.view(-1), labels, ids, n, check=check)

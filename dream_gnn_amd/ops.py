@@ -1470,6 +1470,59 @@ def pair_mlp_rank_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: t
                            % (X.shape[0], C.shape[0]))
     return logit, above, total
 
+
+# ---------------------------------------------------------------------------------------------
+# curve areas — exact AUROC / AUPR of scored samples on the device (evaluation.py:55-65)
+# ---------------------------------------------------------------------------------------------
+_CURVE_FLAGS = ("a score is NaN", "a label is neither 0 nor 1", "a segment id is out of range")
+
+
+class CurveStats:
+    """What :func:`curve_areas` returns, all on the device, one entry per segment (one entry without segments):
+    int64 ``P``, ``N`` (positives, negatives), ``tp``, ``fp`` (those with ``score >= threshold``), ``groups`` (distinct
+    scores), ``u2`` (twice the Mann-Whitney count), float64 ``auroc``, ``aupr`` and the int32 flag word ``info``
+    (bit 0 NaN score, bit 1 label not 0 / 1, bit 2 segment id out of range).  Nothing here reads a value back."""
+
+    def __init__(self, count: torch.Tensor, area: torch.Tensor, info: torch.Tensor):
+        self.count, self.area, self.info = count, area, info
+        self.P, self.N, self.tp, self.fp, self.groups, self.u2 = count.unbind(1)
+        self.auroc, self.aupr = area.unbind(1)
+
+    def accuracy(self) -> torch.Tensor:
+        """``(TP + TN) / (P + N)`` at the threshold (evaluation.py:68), float64 per segment; NaN for an empty one."""
+        return (self.tp + (self.N - self.fp)).double() / (self.P + self.N).double()
+
+    def f1(self) -> torch.Tensor:
+        """``2 TP / (2 TP + FP + FN)`` at the threshold (evaluation.py:70), float64 per segment; NaN where that is 0 / 0."""
+        return (2 * self.tp).double() / (self.tp + self.fp + self.P).double()
+
+    def macro(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``nanmean`` of ``auroc`` and of ``aupr`` over the segments: two float64 scalars on the device."""
+        return torch.nanmean(self.auroc), torch.nanmean(self.aupr)
+
+
+def curve_areas(score: torch.Tensor, label: torch.Tensor, segment: Optional[torch.Tensor] = None, n_segments: int = 0,
+                threshold: float = 0.0, check: bool = True) -> CurveStats:
+    """Exact trapezoid AUROC and AUPR of ``score`` (fp32, any shape) against ``label`` (fp32, bool or integer; positive
+    iff != 0), computed on the device by a sort and a scan (``dgmi_curve_areas_f32``, definition in
+    ``include/dgmi_curve.h``): what ``harness.auroc_aupr`` computes on the host, with ties between scores handled as one
+    threshold.  With ``segment`` (int32 / int64 ids in ``[0, n_segments)``) every segment gets its own statistics, e.g.
+    per disease.  ``threshold`` is the logit cut of ``tp`` / ``fp`` (0 is probability 0.5).
+
+    ``check=True`` reads the flag word, which synchronises once, and raises ``RuntimeError`` naming a set flag.
+    ``check=False`` reads nothing back: the form to queue between replays of a captured training step; the flags stay
+    in ``CurveStats.info``.  Not differentiable."""
+    _require_device(score, label, segment)
+    n_segments = int(n_segments)
+    if (segment is None) != (n_segments == 0):
+        raise ValueError("segment ids and n_segments > 0 go together")
+    stats = CurveStats(*_T.curve_areas(score.detach(), label, segment, n_segments, float(threshold)))
+    if check:
+        flags = int(stats.info[0])
+        if flags:
+            raise RuntimeError("curve_areas: " + "; ".join(m for b, m in enumerate(_CURVE_FLAGS) if flags >> b & 1))
+    return stats
+
 # ---------------------------------------------------------------------------------------------
 # (D3) edge-dropout selection — augmentation.py:48-52, 114-118
 # ---------------------------------------------------------------------------------------------
