@@ -1,6 +1,7 @@
-// dgmi_pair_score.h — the decoder-MLP pair scorer shared by the two pair rankings (gfx950): the global top-k of
-// dgmi_pairs.hip and the per-row top-k of dgmi_pairs_rows.hip.  One place for the arithmetic, so that both return the
-// same bits for the same pair.
+// dgmi_pair_score.h — the decoder-MLP pair scorer shared by every pair kernel (gfx950): the global top-k of
+// dgmi_pairs.hip, the per-row top-k of dgmi_pairs_rows.hip, the emit of dgmi_pairs_above.hip and the list scorer and
+// count scan of dgmi_pairs_given.hip.  One place for the arithmetic, so that all return the same bits for the same pair.
+// What else they share is in dgmi_pair_stream.h.
 //
 // A wave holds 32 "lane" rows (one per lane column; lane l keeps k = 64 (l >> 5) + s of row l & 31) and streams
 // "stream" rows two at a time.  For stream row i the 64 x 32 block W2 . relu(S[i] + L[j0:j0+32]) is 2 x 64

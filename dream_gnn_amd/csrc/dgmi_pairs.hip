@@ -13,7 +13,9 @@
 // (Q: per task), P rows come from LDS as a two-address broadcast.  Two drugs x two row halves = 4 independent
 // accumulators per wave, the condition for the 64-cycle f32 MFMA to issue back to back from one wave per SIMD.
 // After the 64 steps each lane sums w3[h] relu(acc + b2[h]) over its 32 rows and adds its partner lane (l ^ 32).
-// The scorer lives in dgmi_pair_score.h, shared with the per-row top-k (dgmi_pairs_rows.hip): same logits, same bits.
+// The scorer lives in dgmi_pair_score.h, shared by every pair kernel: same logits, same bits.  The ranking key, the
+// ballot append, the task geometry and the host prologue are those of dgmi_pair_stream.h, shared with the emit kernel
+// of dgmi_pairs_above.hip; the task loop and the sort stay here (that header says why).
 //
 // Top-k.  A persistent grid of one workgroup per CU takes (drug chunk, 128-disease group) tasks in drug-major order,
 // so all workgroups read the same P rows at the same time.  Each keeps, in LDS, its best-k list followed by an append
@@ -26,27 +28,14 @@
 #include <stdint.h>
 
 #include "dgmi.h"
-#include "dgmi_pair_score.h"
+#include "dgmi_pair_stream.h"
 #include "dgmi_pairs.h"
 
 namespace {
 
-constexpr int kThreads = 256;            // 4 waves; each owns 32 diseases of the task's group
-constexpr int kGroupCols = 128;          // diseases per task
-constexpr int kMaxChunk = 64;            // drugs per task (at most)
-constexpr int kPStride = 2 * 68;         // a P row in LDS: two 64-float halves, 4 floats apart (conflict-free broadcast)
 constexpr int kSortCap = 2048;           // LDS list + append buffer, entries
-constexpr int kSub = 4;                  // drugs between two fill checks: at most kSub * kGroupCols appends
-constexpr int kGrid = 256;               // persistent workgroups (one per CU)
-constexpr int kMergeThreads = 1024;
-constexpr int kMergeCap = 8192;          // entries one merge workgroup sorts
-constexpr int kMaxFan = 64;
-constexpr size_t kAlign = 256;
-
-// the full ranking key: logit descending, then drug ascending, then disease ascending
-__device__ __forceinline__ bool better(uint32_t fa, uint32_t ia, uint32_t ja, uint32_t fb, uint32_t ib, uint32_t jb) {
-  return fa > fb || (fa == fb && (ia < ib || (ia == ib && ja < jb)));
-}
+constexpr int kMergeThreads = 1024;      // this file's own: one list of up to kMergeCap entries per workgroup, dynamic LDS
+constexpr int kMergeCap = 8192;          // entries one merge workgroup sorts (the per-row merge sorts 4096 in static LDS)
 
 // Bitonic sort of n (a power of two) entries of the SoA list (f, i, j) into descending key order, all threads of the
 // block.  Ends with a barrier.
@@ -57,7 +46,7 @@ __device__ void block_sort_desc(uint32_t* f, uint32_t* ii, uint32_t* jj, int n, 
         const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
         const bool desc = (lo & size) == 0;
         const uint32_t fl = f[lo], fh = f[hi], il = ii[lo], ih = ii[hi], jl = jj[lo], jh = jj[hi];
-        if (better(fh, ih, jh, fl, il, jl) == desc) {
+        if (PairKey::better(fh, ih, jh, fl, il, jl) == desc) {
           f[lo] = fh;
           f[hi] = fl;
           ii[lo] = ih;
@@ -69,12 +58,6 @@ __device__ void block_sort_desc(uint32_t* f, uint32_t* ii, uint32_t* jj, int n, 
       __syncthreads();
     }
   }
-}
-
-__device__ __forceinline__ void set_pad(uint32_t* f, uint32_t* ii, uint32_t* jj, int e) {
-  f[e] = 0u;  // below every candidate: a real NaN pair has the same key but smaller ids
-  ii[e] = 0xffffffffu;
-  jj[e] = 0xffffffffu;
 }
 
 struct ScoreArgs {
@@ -98,7 +81,7 @@ struct ScoreArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
-  __shared__ __attribute__((aligned(16))) float p_lds[kMaxChunk * kPStride];
+  __shared__ __attribute__((aligned(16))) float p_lds[kMaxChunk * kRowStride];
   __shared__ uint32_t ef[kSortCap], ei[kSortCap], ej[kSortCap];
   __shared__ int s_used;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -117,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
     const int n = s_used;
     int np = 1;
     while (np < n) np <<= 1;
-    for (int e = n + tid; e < np; e += kThreads) set_pad(ef, ei, ej, e);
+    for (int e = n + tid; e < np; e += kThreads) PairKey{ef, ei, ej}.pad(e);
     __syncthreads();
     block_sort_desc(ef, ei, ej, np, tid, kThreads);
     const int keep = n < k ? n : k;
@@ -135,22 +118,8 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
   // offer lane `col`'s pair (i, j) of one drug; lanes 32..63 hold the same pairs and never append
   auto offer = [&](bool valid, float logit, uint32_t i, uint32_t j) {
     const uint32_t f = order_key(logit);
-    const bool q = half == 0 && valid && (!full || better(f, i, j, tf, ti, tj));
-    const uint64_t m = __ballot(q);
-    if (m != 0) {
-      const int leader = __ffsll((unsigned long long)m) - 1;
-      int base = 0;
-      if (lane == leader) base = atomicAdd(&s_used, __popcll(m));
-      base = __shfl(base, leader);
-      if (q) {
-        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (pos < kSortCap) {  // always: at most kSub * kGroupCols appends between two checks
-          ef[pos] = f;
-          ei[pos] = i;
-          ej[pos] = j;
-        }
-      }
-    }
+    const bool q = half == 0 && valid && (!full || PairKey::better(f, i, j, tf, ti, tj));
+    ballot_append(q, f, i, j, lane, &s_used, ef, ei, ej, kSortCap);
   };
 
   for (int64_t task = blockIdx.x; task < a.n_tasks; task += gridDim.x) {
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
       const int r = e >> 5, c4 = e & 31;
       const int row = r < nd ? i0 + r : a.n_drug - 1;
       const float4 v = *reinterpret_cast<const float4*>(a.P + (int64_t)row * a.ldp + 4 * c4);
-      *reinterpret_cast<float4*>(p_lds + r * kPStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+      *reinterpret_cast<float4*>(p_lds + r * kRowStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
     }
     const int j0 = g * kGroupCols + wave * 32;  // this wave's 32 diseases
     const int j = j0 + col;
@@ -181,8 +150,8 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_topk_kernel(ScoreArgs a) {
         const int db = has_b ? da + 1 : da;
         const uint32_t kwa = words ? bm[(int64_t)(i0 + da) * a.nwords] : 0u;
         const uint32_t kwb = words ? bm[(int64_t)(i0 + db) * a.nwords] : 0u;
-        const float* pa = p_lds + da * kPStride + 68 * half;
-        const float* pb = p_lds + db * kPStride + 68 * half;
+        const float* pa = p_lds + da * kRowStride + 68 * half;
+        const float* pb = p_lds + db * kRowStride + 68 * half;
         float la, lb;
         score_two(pa, pb, q, dec, la, lb);
         offer(col_ok && !((kwa >> col) & 1u), la, (uint32_t)(i0 + da), (uint32_t)j);
@@ -241,7 +210,7 @@ __global__ __launch_bounds__(kMergeThreads) void pair_merge_kernel(const uint32_
       ii[e] = in_i[src];
       jj[e] = in_j[src];
     } else {
-      set_pad(f, ii, jj, e);
+      PairKey{f, ii, jj}.pad(e);
     }
   }
   __syncthreads();
@@ -268,11 +237,9 @@ __global__ __launch_bounds__(kMergeThreads) void pair_merge_kernel(const uint32_
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 
-inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
 struct Plan {
-  int chunk, n_groups, grid, fan;
-  int64_t n_tasks, nwords;
+  LaneColumnPlan tasks;
+  int fan;
   size_t bitmap, lists_a, lists_b, total;  // byte offsets / size
 };
 
@@ -280,22 +247,13 @@ size_t lists_bytes(int64_t n_lists, int k) { return align_up((size_t)n_lists * (
 
 Plan make_plan(int64_t n_drug, int64_t n_dis, int k) {
   Plan p;
-  p.n_groups = (int)((n_dis + kGroupCols - 1) / kGroupCols);
-  // enough tasks for ~4 per workgroup on small problems; 64-drug chunks otherwise
-  p.chunk = kMaxChunk;
-  while (p.chunk > 2 && ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups < 4 * kGrid) p.chunk >>= 1;
-  p.n_tasks = ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups;
-  p.grid = (int)(p.n_tasks < kGrid ? p.n_tasks : kGrid);
-  int kp = 1;
-  while (kp < k) kp <<= 1;
-  p.fan = kMergeCap / kp;
-  if (p.fan > kMaxFan) p.fan = kMaxFan;
+  p.tasks = lane_column_plan(n_drug, n_dis);
+  p.fan = merge_fan(kMergeCap, k);
   if (p.fan < 2) p.fan = 2;
-  p.nwords = (n_dis + 31) / 32;
   p.bitmap = 0;
-  p.lists_a = align_up((size_t)n_drug * (size_t)p.nwords * 4);
-  p.lists_b = p.lists_a + lists_bytes(p.grid, k);
-  p.total = p.lists_b + lists_bytes((p.grid + p.fan - 1) / p.fan, k);
+  p.lists_a = bitmap_bytes(n_drug, p.tasks.nwords);
+  p.lists_b = p.lists_a + lists_bytes(p.tasks.grid, k);
+  p.total = p.lists_b + lists_bytes((p.tasks.grid + p.fan - 1) / p.fan, k);
   return p;
 }
 
@@ -315,8 +273,6 @@ Lists lists_at(void* ws, size_t off, int64_t n_lists, int k) {
   return l;
 }
 
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -331,14 +287,10 @@ DGMI_API int dgmi_pair_mlp_topk_f32(const float* P, int64_t ldp, int64_t n_drug,
                                     const int32_t* known_drug, const int32_t* known_dis, int64_t n_known, int32_t k,
                                     int32_t* out_drug, int32_t* out_dis, float* out_logit, int32_t* out_info, void* workspace,
                                     size_t workspace_bytes, dgmi_stream_t stream) {
-  if (h1 != kH1 || h2 != kH2 || k < 1 || k > DGMI_PAIR_TOPK_MAX_K) return DGMI_ERR_INVALID_ARG;
-  if (n_drug < 0 || n_dis < 0 || n_known < 0 || n_drug > INT32_MAX || n_dis > INT32_MAX) return DGMI_ERR_INVALID_ARG;
+  if (!check_pair_extents(h1, h2, n_drug, n_dis, n_known) || k < 1 || k > DGMI_PAIR_TOPK_MAX_K) return DGMI_ERR_INVALID_ARG;
   if (n_drug == 0 || n_dis == 0) return DGMI_OK;
-  if (P == nullptr || Q == nullptr || W2 == nullptr || b2 == nullptr || w3 == nullptr || b3 == nullptr || out_drug == nullptr ||
-      out_dis == nullptr || out_logit == nullptr || out_info == nullptr)
-    return DGMI_ERR_INVALID_ARG;
-  if (n_known > 0 && (known_drug == nullptr || known_dis == nullptr)) return DGMI_ERR_INVALID_ARG;
-  if (ldp < kH1 || ldq < kH1 || ldp % 4 != 0 || ldq % 4 != 0 || misaligned(P) || misaligned(Q) || misaligned(W2))
+  if (out_drug == nullptr || out_dis == nullptr || out_logit == nullptr || out_info == nullptr) return DGMI_ERR_INVALID_ARG;
+  if (!check_known(known_drug, known_dis, n_known) || !check_pair_operands(P, ldp, Q, ldq, W2, b2, w3, b3))
     return DGMI_ERR_INVALID_ARG;
   const Plan plan = make_plan(n_drug, n_dis, k);
   if (workspace == nullptr || workspace_bytes < plan.total) return DGMI_ERR_WORKSPACE;
@@ -348,17 +300,14 @@ DGMI_API int dgmi_pair_mlp_topk_f32(const float* P, int64_t ldp, int64_t n_drug,
   uint32_t* bitmap = nullptr;
   if (n_known > 0) {
     bitmap = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + plan.bitmap);
-    if (hipMemsetAsync(bitmap, 0, (size_t)n_drug * (size_t)plan.nwords * 4, s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    int64_t blocks = (n_known + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, known_drug, known_dis, n_known,
-                       (int)n_drug, (int)n_dis, plan.nwords, bitmap, out_info);
+    if (build_known_bitmap(known_drug, known_dis, n_known, n_drug, n_dis, plan.tasks.nwords, bitmap, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
   }
 
-  Lists la = lists_at(workspace, plan.lists_a, plan.grid, k);
-  ScoreArgs args{P, ldp, Q, ldq, (int)n_drug, (int)n_dis, W2, b2, w3, b3, bitmap, plan.nwords, k, plan.chunk,
-                 plan.n_groups, plan.n_tasks, la.f, la.i, la.j, la.n};
-  hipLaunchKernelGGL(pair_mlp_topk_kernel, dim3((unsigned)plan.grid), dim3(kThreads), 0, s, args);
+  Lists la = lists_at(workspace, plan.lists_a, plan.tasks.grid, k);
+  ScoreArgs args{P, ldp, Q, ldq, (int)n_drug, (int)n_dis, W2, b2, w3, b3, bitmap, plan.tasks.nwords, k, plan.tasks.chunk,
+                 plan.tasks.n_groups, plan.tasks.n_tasks, la.f, la.i, la.j, la.n};
+  hipLaunchKernelGGL(pair_mlp_topk_kernel, dim3((unsigned)plan.tasks.grid), dim3(kThreads), 0, s, args);
   if (hipGetLastError() != hipSuccess) return DGMI_ERR_LAUNCH;
 
   const size_t lds = (size_t)kMergeCap * 12;
@@ -366,12 +315,12 @@ DGMI_API int dgmi_pair_mlp_topk_f32(const float* P, int64_t ldp, int64_t n_drug,
                           (int)lds) != hipSuccess)
     return DGMI_ERR_LAUNCH;
   // rounds: lists A -> B -> A ... until one workgroup merges what is left into the result
-  int n_lists = plan.grid;
+  int n_lists = plan.tasks.grid;
   bool in_a = true;
   for (;;) {
     const int out_lists = (n_lists + plan.fan - 1) / plan.fan;
-    const Lists src = in_a ? la : lists_at(workspace, plan.lists_b, (plan.grid + plan.fan - 1) / plan.fan, k);
-    const Lists dst = in_a ? lists_at(workspace, plan.lists_b, (plan.grid + plan.fan - 1) / plan.fan, k) : la;
+    const Lists src = in_a ? la : lists_at(workspace, plan.lists_b, (plan.tasks.grid + plan.fan - 1) / plan.fan, k);
+    const Lists dst = in_a ? lists_at(workspace, plan.lists_b, (plan.tasks.grid + plan.fan - 1) / plan.fan, k) : la;
     const bool last = out_lists == 1;
     int kp = 1;
     while (kp < (n_lists < plan.fan ? n_lists : plan.fan) * k) kp <<= 1;

@@ -21,18 +21,11 @@
 #include "dgmi.h"
 #include "dgmi_above.h"
 #include "dgmi_kernels.h"
-#include "dgmi_pair_score.h"
+#include "dgmi_pair_stream.h"
 
 namespace {
 
-constexpr int kThreads = 256;            // 4 waves; each owns 32 diseases of the task's group
-constexpr int kGroupCols = 128;          // diseases per task
-constexpr int kMaxChunk = 64;            // drugs per task (at most)
-constexpr int kPStride = 2 * 68;         // a P row in LDS: two 64-float halves, 4 floats apart (conflict-free broadcast)
 constexpr int kStageCap = 2048;          // LDS staging buffer, records
-constexpr int kSub = 4;                  // drugs between two fill checks: at most kSub * kGroupCols appends
-constexpr int kGrid = 256;               // persistent workgroups (one per CU)
-constexpr size_t kAlign = 256;
 
 struct EmitArgs {
   const float* P;
@@ -57,7 +50,7 @@ struct EmitArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void pair_mlp_emit_kernel(EmitArgs a) {
-  __shared__ __attribute__((aligned(16))) float p_lds[kMaxChunk * kPStride];
+  __shared__ __attribute__((aligned(16))) float p_lds[kMaxChunk * kRowStride];
   __shared__ uint32_t ef[kStageCap], ei[kStageCap], ej[kStageCap];
   __shared__ int s_used;
   __shared__ unsigned long long s_base;
@@ -95,21 +88,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_emit_kernel(EmitArgs a) {
   auto offer = [&](bool valid, float logit, uint32_t i, uint32_t j) {
     const uint32_t f = order_key(logit);
     const bool q = half == 0 && valid && f >= cut;
-    const uint64_t m = __ballot(q);
-    if (m != 0) {
-      const int leader = __ffsll((unsigned long long)m) - 1;
-      int base = 0;
-      if (lane == leader) base = atomicAdd(&s_used, __popcll(m));
-      base = __shfl(base, leader);
-      if (q) {
-        const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (pos < kStageCap) {  // always: at most kSub * kGroupCols appends between two checks
-          ef[pos] = f;
-          ei[pos] = i;
-          ej[pos] = j;
-        }
-      }
-    }
+    ballot_append(q, f, i, j, lane, &s_used, ef, ei, ej, kStageCap);
   };
 
   for (int64_t task = blockIdx.x; task < a.n_tasks; task += gridDim.x) {
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_emit_kernel(EmitArgs a) {
       const int r = e >> 5, c4 = e & 31;
       const int row = r < nd ? i0 + r : a.n_drug - 1;
       const float4 v = *reinterpret_cast<const float4*>(a.P + (int64_t)row * a.ldp + 4 * c4);
-      *reinterpret_cast<float4*>(p_lds + r * kPStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+      *reinterpret_cast<float4*>(p_lds + r * kRowStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
     }
     const int j0 = g * kGroupCols + wave * 32;  // this wave's 32 diseases
     const int j = j0 + col;
@@ -140,8 +119,8 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_emit_kernel(EmitArgs a) {
         const int db = has_b ? da + 1 : da;
         const uint32_t kwa = words ? bm[(int64_t)(i0 + da) * a.nwords] : 0u;
         const uint32_t kwb = words ? bm[(int64_t)(i0 + db) * a.nwords] : 0u;
-        const float* pa = p_lds + da * kPStride + 68 * half;
-        const float* pb = p_lds + db * kPStride + 68 * half;
+        const float* pa = p_lds + da * kRowStride + 68 * half;
+        const float* pb = p_lds + db * kRowStride + 68 * half;
         float la, lb;
         score_two(pa, pb, q, dec, la, lb);
         offer(col_ok && !((kwa >> col) & 1u), la, (uint32_t)(i0 + da), (uint32_t)j);
@@ -171,30 +150,6 @@ __global__ __launch_bounds__(256) void records_from_key_kernel(const int32_t* __
   if (e < n) logit[e] = key_logit(~(uint32_t)key[e]);
 }
 
-inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-struct Plan {
-  int chunk, n_groups, grid;
-  int64_t n_tasks, nwords;
-  size_t total;  // bytes: the known-pair bitmap
-};
-
-// the task geometry of dgmi_pairs.hip (make_plan), without the lists
-Plan make_plan(int64_t n_drug, int64_t n_dis) {
-  Plan p;
-  p.n_groups = (int)((n_dis + kGroupCols - 1) / kGroupCols);
-  // enough tasks for ~4 per workgroup on small problems; 64-drug chunks otherwise
-  p.chunk = kMaxChunk;
-  while (p.chunk > 2 && ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups < 4 * kGrid) p.chunk >>= 1;
-  p.n_tasks = ((n_drug + p.chunk - 1) / p.chunk) * p.n_groups;
-  p.grid = (int)(p.n_tasks < kGrid ? p.n_tasks : kGrid);
-  p.nwords = (n_dis + 31) / 32;
-  p.total = align_up((size_t)n_drug * (size_t)p.nwords * 4);
-  return p;
-}
-
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 constexpr int kIdBits = 31;   // ids are non-negative int32
 constexpr int kKeyBits = 32;
 
@@ -204,7 +159,7 @@ extern "C" {
 
 DGMI_API size_t dgmi_pair_emit_workspace_bytes(int64_t n_drug, int64_t n_dis) {
   if (n_drug <= 0 || n_dis <= 0 || n_drug > INT32_MAX || n_dis > INT32_MAX) return 0;
-  return make_plan(n_drug, n_dis).total;
+  return bitmap_bytes(n_drug, lane_column_plan(n_drug, n_dis).nwords);  // the known-pair bitmap, nothing else
 }
 
 DGMI_API int dgmi_pair_mlp_emit_f32(const float* P, int64_t ldp, int64_t n_drug, const float* Q, int64_t ldq, int64_t n_dis,
@@ -212,36 +167,29 @@ DGMI_API int dgmi_pair_mlp_emit_f32(const float* P, int64_t ldp, int64_t n_drug,
                                     const int32_t* known_drug, const int32_t* known_dis, int64_t n_known, float min_logit,
                                     int64_t capacity, int32_t* out_drug, int32_t* out_dis, float* out_logit, int64_t* out_count,
                                     int32_t* out_info, void* workspace, size_t workspace_bytes, dgmi_stream_t stream) {
-  if (h1 != kH1 || h2 != kH2 || capacity < 0 || capacity > DGMI_PAIR_EMIT_MAX_RECORDS) return DGMI_ERR_INVALID_ARG;
-  if (n_drug < 0 || n_dis < 0 || n_known < 0 || n_drug > INT32_MAX || n_dis > INT32_MAX) return DGMI_ERR_INVALID_ARG;
+  if (!check_pair_extents(h1, h2, n_drug, n_dis, n_known) || capacity < 0 || capacity > DGMI_PAIR_EMIT_MAX_RECORDS)
+    return DGMI_ERR_INVALID_ARG;
   if (out_count == nullptr || out_info == nullptr) return DGMI_ERR_INVALID_ARG;
   if (capacity > 0 && (out_drug == nullptr || out_dis == nullptr || out_logit == nullptr)) return DGMI_ERR_INVALID_ARG;
+  // an empty problem takes any operands and no workspace: the two counters are all that is written
   const bool empty = n_drug == 0 || n_dis == 0;
+  LaneColumnPlan plan{};
   if (!empty) {
-    if (P == nullptr || Q == nullptr || W2 == nullptr || b2 == nullptr || w3 == nullptr || b3 == nullptr) return DGMI_ERR_INVALID_ARG;
-    if (n_known > 0 && (known_drug == nullptr || known_dis == nullptr)) return DGMI_ERR_INVALID_ARG;
-    if (ldp < kH1 || ldq < kH1 || ldp % 4 != 0 || ldq % 4 != 0 || misaligned(P) || misaligned(Q) || misaligned(W2))
+    if (!check_known(known_drug, known_dis, n_known) || !check_pair_operands(P, ldp, Q, ldq, W2, b2, w3, b3))
       return DGMI_ERR_INVALID_ARG;
+    plan = lane_column_plan(n_drug, n_dis);
+    if (workspace == nullptr || workspace_bytes < bitmap_bytes(n_drug, plan.nwords)) return DGMI_ERR_WORKSPACE;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (empty) {
-    if (hipMemsetAsync(out_count, 0, sizeof(int64_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    return DGMI_OK;
-  }
-  const Plan plan = make_plan(n_drug, n_dis);
-  if (workspace == nullptr || workspace_bytes < plan.total) return DGMI_ERR_WORKSPACE;
 
   if (hipMemsetAsync(out_count, 0, sizeof(int64_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
   if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
+  if (empty) return DGMI_OK;
   uint32_t* bitmap = nullptr;
   if (n_known > 0) {
     bitmap = static_cast<uint32_t*>(workspace);
-    if (hipMemsetAsync(bitmap, 0, (size_t)n_drug * (size_t)plan.nwords * 4, s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    int64_t blocks = (n_known + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, known_drug, known_dis, n_known,
-                       (int)n_drug, (int)n_dis, plan.nwords, bitmap, out_info);
+    if (build_known_bitmap(known_drug, known_dis, n_known, n_drug, n_dis, plan.nwords, bitmap, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
   }
   EmitArgs args{P, ldp, Q, ldq, (int)n_drug, (int)n_dis, W2, b2, w3, b3, bitmap, plan.nwords, plan.chunk, plan.n_groups,
                 plan.n_tasks, min_logit, (unsigned long long)capacity, out_drug, out_dis, out_logit,

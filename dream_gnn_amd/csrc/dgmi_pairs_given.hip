@@ -21,25 +21,12 @@
 
 #include "dgmi.h"
 #include "dgmi_given.h"
-#include "dgmi_pair_score.h"
+#include "dgmi_pair_stream.h"
 
 namespace {
 
-constexpr int kThreads = 256;             // 4 waves
-constexpr int kCols = 32;                 // listed pairs per wave (one per lane column)
+constexpr int kCols = kLaneRows;          // listed pairs per wave (one per lane column)
 constexpr int kListBlock = 4 * kCols;     // listed pairs per workgroup of the list scorer
-constexpr int kChunk = 128;               // candidate rows staged in LDS at a time
-constexpr int kCStride = 2 * 68;          // a candidate row in LDS: two 64-float halves, 4 floats apart
-constexpr int kGrid = 256;                // persistent workgroups (one per CU)
-constexpr int kTaskTarget = 16 * kGrid;   // tasks wanted: >= 16 rounds keeps the last one short
-constexpr int kMaxSeg = 256;              // candidate segments per pair, at most
-constexpr int kMinSeg = 32;               // candidates per segment, at least
-constexpr size_t kAlign = 256;
-
-// the per-row ranking key: logit descending, then candidate ascending (dgmi_pairs_rows.hip)
-__device__ __forceinline__ bool better(uint32_t fa, uint32_t ca, uint32_t fb, uint32_t cb) {
-  return fa > fb || (fa == fb && ca < cb);
-}
 
 struct GivenArgs {
   const float* X;  // query side, on the lane columns
@@ -65,10 +52,10 @@ struct GivenArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void pair_mlp_score_list_kernel(GivenArgs a) {
-  __shared__ __attribute__((aligned(16))) float c_lds[kListBlock * kCStride];
+  __shared__ __attribute__((aligned(16))) float c_lds[kListBlock * kRowStride];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
-  float* const rows = c_lds + wave * kCols * kCStride;  // this wave's 32 candidate rows
+  float* const rows = c_lds + wave * kCols * kRowStride;  // this wave's 32 candidate rows
 
   PairDecoder dec;
   load_decoder(dec, a.W2, a.b2, a.w3, a.b3, half, col);
@@ -87,11 +74,11 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_score_list_kernel(GivenArgs
       const int idx = it * 64 + lane, r = idx >> 5, c4 = idx & 31;
       const int src = __shfl(cr, r);  // the candidate row of column r
       const float4 v = *reinterpret_cast<const float4*>(a.C + (int64_t)src * a.ldc + 4 * c4);
-      *reinterpret_cast<float4*>(rows + r * kCStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+      *reinterpret_cast<float4*>(rows + r * kRowStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
     }
     __syncthreads();
     float logit;
-    score_one(rows + col * kCStride + 68 * half, x, dec, logit);
+    score_one(rows + col * kRowStride + 68 * half, x, dec, logit);
     if (half == 0 && listed) {
       a.out_logit[e] = ok ? logit : __uint_as_float(0x7fc00000u);
       if (a.out_above != nullptr) {
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_score_list_kernel(GivenArgs
 }
 
 __global__ __launch_bounds__(kThreads) void pair_count_scan_kernel(GivenArgs a) {
-  __shared__ __attribute__((aligned(16))) float c_lds[kChunk * kCStride];
+  __shared__ __attribute__((aligned(16))) float c_lds[kChunk * kRowStride];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, col = lane & 31;
 
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void pair_count_scan_kernel(GivenArgs a) 
     auto count = [&](bool valid, uint32_t known_word, float logit, uint32_t cand) {
       if (valid && cand != ec && !((known_word >> qbit) & 1u)) {
         ++total;
-        if (better(order_key(logit), cand, ef, ec)) ++above;
+        if (RowKey::better(order_key(logit), cand, ef, ec)) ++above;
       }
     };
 
@@ -141,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void pair_count_scan_kernel(GivenArgs a) 
       for (int i = tid; i < nc * 32; i += kThreads) {
         const int r = i >> 5, c4 = i & 31;
         const float4 v = *reinterpret_cast<const float4*>(a.C + (int64_t)(cc + r) * a.ldc + 4 * c4);
-        *reinterpret_cast<float4*>(c_lds + r * kCStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+        *reinterpret_cast<float4*>(c_lds + r * kRowStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
       }
       __syncthreads();
       const int per = (nc + 7) / 8 * 2;  // an even share of the chunk per wave: a short segment still uses all four
@@ -153,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void pair_count_scan_kernel(GivenArgs a) 
         const uint32_t kwa = words ? bm[(int64_t)(cc + da) * a.nwords] : 0u;
         const uint32_t kwb = words ? bm[(int64_t)(cc + db) * a.nwords] : 0u;
         float la, lb;
-        score_two(c_lds + da * kCStride + 68 * half, c_lds + db * kCStride + 68 * half, x, dec, la, lb);
+        score_two(c_lds + da * kRowStride + 68 * half, c_lds + db * kRowStride + 68 * half, x, dec, la, lb);
         count(ok, kwa, la, (uint32_t)(cc + da));
         count(ok && has_b, kwb, lb, (uint32_t)(cc + db));
       }
@@ -183,66 +170,32 @@ __global__ __launch_bounds__(256) void given_empty_kernel(int64_t n_pairs, float
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 
-inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-struct GivenPlan {
-  int n_groups, n_seg, seg, grid;
-  int64_t n_tasks, nwords;
-  size_t total;  // the known-pair bitmap
-};
-
-GivenPlan make_given_plan(int64_t n_query, int64_t n_cand, int64_t n_pairs) {
-  GivenPlan p;
-  p.n_groups = (int)((n_pairs + kCols - 1) / kCols);
-  // split the candidate axis until there are ~16 tasks per workgroup: 10 000 listed pairs take 14 segments, one takes 256
-  int64_t s = (kTaskTarget + p.n_groups - 1) / p.n_groups;
-  if (s > kMaxSeg) s = kMaxSeg;
-  if (s > (n_cand + kMinSeg - 1) / kMinSeg) s = (n_cand + kMinSeg - 1) / kMinSeg;
-  if (s < 1) s = 1;
-  p.seg = (int)((n_cand + s - 1) / s);
-  p.n_seg = (int)((n_cand + p.seg - 1) / p.seg);
-  p.n_tasks = (int64_t)p.n_groups * p.n_seg;
-  p.grid = (int)(p.n_tasks < kGrid ? p.n_tasks : kGrid);
-  p.nwords = (n_query + 31) / 32;
-  p.total = align_up((size_t)n_cand * (size_t)p.nwords * 4);
-  return p;
-}
-
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 // Both entry points: out_above == nullptr scores the list only.
 int given_launch(const float* X, int64_t ldx, int64_t n_query, const float* C, int64_t ldc, int64_t n_cand, int32_t h1,
                  int32_t h2, const float* W2, const float* b2, const float* w3, const float* b3, const int32_t* pair_query,
                  const int32_t* pair_cand, int64_t n_pairs, const int32_t* known_query, const int32_t* known_cand,
                  int64_t n_known, bool rank, float* out_logit, int32_t* out_above, int32_t* out_total, int32_t* out_info,
                  void* workspace, size_t workspace_bytes, dgmi_stream_t stream) {
-  if (h1 != kH1 || h2 != kH2) return DGMI_ERR_INVALID_ARG;
-  if (n_query < 0 || n_cand < 0 || n_pairs < 0 || n_known < 0 || n_query > INT32_MAX || n_cand > INT32_MAX || n_pairs > INT32_MAX)
-    return DGMI_ERR_INVALID_ARG;
+  if (!check_pair_extents(h1, h2, n_query, n_cand, n_known) || n_pairs < 0 || n_pairs > INT32_MAX) return DGMI_ERR_INVALID_ARG;
   if (n_pairs == 0) return DGMI_OK;
   if (pair_query == nullptr || pair_cand == nullptr || out_logit == nullptr || out_info == nullptr) return DGMI_ERR_INVALID_ARG;
   if (rank && (out_above == nullptr || out_total == nullptr)) return DGMI_ERR_INVALID_ARG;
-  if (n_known > 0 && (known_query == nullptr || known_cand == nullptr)) return DGMI_ERR_INVALID_ARG;
+  if (!check_known(known_query, known_cand, n_known)) return DGMI_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_query == 0 || n_cand == 0) {
+  if (n_query == 0 || n_cand == 0) {  // every listed pair is out of range, whatever the operands
     if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
     int64_t blocks = (n_pairs + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(given_empty_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n_pairs, out_logit, out_above, out_total,
                        out_info);
-    if (n_known > 0) {  // every known id is out of range: flag it, write nothing
-      int64_t kb = (n_known + 255) / 256;
-      if (kb > 4096) kb = 4096;
-      hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)kb), dim3(256), 0, s, known_cand, known_query, n_known, 0, 0,
-                         (int64_t)0, static_cast<uint32_t*>(nullptr), out_info);
-    }
+    // every known id is out of range: flag it
+    if (n_known > 0 && build_known_bitmap(known_cand, known_query, n_known, 0, 0, 0, nullptr, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
     return hipGetLastError() == hipSuccess ? DGMI_OK : DGMI_ERR_LAUNCH;
   }
-  if (X == nullptr || C == nullptr || W2 == nullptr || b2 == nullptr || w3 == nullptr || b3 == nullptr) return DGMI_ERR_INVALID_ARG;
-  if (ldx < kH1 || ldc < kH1 || ldx % 4 != 0 || ldc % 4 != 0 || misaligned(X) || misaligned(C) || misaligned(W2))
-    return DGMI_ERR_INVALID_ARG;
-  const GivenPlan plan = make_given_plan(n_query, n_cand, n_pairs);
-  if (rank && (workspace == nullptr || workspace_bytes < plan.total)) return DGMI_ERR_WORKSPACE;
+  if (!check_pair_operands(X, ldx, C, ldc, W2, b2, w3, b3)) return DGMI_ERR_INVALID_ARG;
+  const SegmentPlan plan = segment_plan(n_pairs, n_cand, n_query);
+  if (rank && (workspace == nullptr || workspace_bytes < bitmap_bytes(n_cand, plan.nwords))) return DGMI_ERR_WORKSPACE;
 
   if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
   GivenArgs args{X, ldx, C, ldc, (int)n_query, (int)n_cand, W2, b2, w3, b3, pair_query, pair_cand, (int)n_pairs, out_logit,
@@ -256,11 +209,8 @@ int given_launch(const float* X, int64_t ldx, int64_t n_query, const float* C, i
 
   if (n_known > 0) {
     uint32_t* bitmap = static_cast<uint32_t*>(workspace);
-    if (hipMemsetAsync(bitmap, 0, (size_t)n_cand * (size_t)plan.nwords * 4, s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    int64_t blocks = (n_known + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, known_cand, known_query, n_known,
-                       (int)n_cand, (int)n_query, plan.nwords, bitmap, out_info);
+    if (build_known_bitmap(known_cand, known_query, n_known, n_cand, n_query, plan.nwords, bitmap, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
     args.bitmap = bitmap;
   }
   hipLaunchKernelGGL(pair_count_scan_kernel, dim3((unsigned)plan.grid), dim3(kThreads), 0, s, args);
@@ -273,7 +223,7 @@ extern "C" {
 
 DGMI_API size_t dgmi_pair_rank_workspace_bytes(int64_t n_query, int64_t n_cand, int64_t n_pairs) {
   if (n_query <= 0 || n_cand <= 0 || n_pairs <= 0 || n_query > INT32_MAX || n_cand > INT32_MAX || n_pairs > INT32_MAX) return 0;
-  return make_given_plan(n_query, n_cand, n_pairs).total;
+  return bitmap_bytes(n_cand, segment_plan(n_pairs, n_cand, n_query).nwords);  // the known-pair bitmap, nothing else
 }
 
 DGMI_API int dgmi_pair_mlp_score_list_f32(const float* X, int64_t ldx, int64_t n_query, const float* C, int64_t ldc,

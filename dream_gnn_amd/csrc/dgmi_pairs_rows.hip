@@ -6,6 +6,9 @@
 // mapping; for per-drug lists Q rows stream where P rows do there.  relu(X + C) = relu(P + Q) bit for bit, and the MFMA
 // operand layout, step order and epilogue order are the shared ones, so every logit equals the global kernel's.
 //
+// The ranking key, the task geometry (segment_plan, shared with the count scan of dgmi_pairs_given.hip) and the host
+// prologue are those of dgmi_pair_stream.h; the candidate loop and the sort stay here (that header says why).
+//
 // Top-k.  A task is (32 query rows, a segment of the candidate axis); a persistent grid of one workgroup per CU takes
 // them segment-major, so concurrent workgroups read the same candidate rows.  The four waves of a workgroup share the
 // task's 32 rows and split each 128-candidate chunk (32 candidates each).  Every row owns a 256-entry LDS region: its
@@ -20,35 +23,20 @@
 #include <stdint.h>
 
 #include "dgmi.h"
-#include "dgmi_pair_score.h"
+#include "dgmi_pair_stream.h"
 #include "dgmi_rank.h"
 
 namespace {
 
-constexpr int kThreads = 256;             // 4 waves, all on the task's 32 query rows
-constexpr int kRows = 32;                 // query rows per task (one per lane column)
-constexpr int kChunk = 128;               // candidate rows staged in LDS at a time
+constexpr int kRows = kLaneRows;          // query rows per task (one per lane column)
 constexpr int kPerWave = kChunk / 4;      // candidates of a chunk per wave
-constexpr int kCStride = 2 * 68;          // a candidate row in LDS: two 64-float halves, 4 floats apart
 constexpr int kRowCap = 256;              // LDS list + append buffer per row, entries
-constexpr int kSub = 4;                   // candidates per wave between two fill checks
 constexpr int kTrigger = kRowCap - 4 * kSub;  // sort when a row holds more: at most 4 kSub appends per row per period
-constexpr int kGrid = 256;                // persistent workgroups (one per CU)
-constexpr int kTaskTarget = 16 * kGrid;   // tasks wanted: >= 16 rounds keeps the last one short
-constexpr int kMaxSeg = 256;              // candidate segments per row, at most
-constexpr int kMinSeg = 32;               // candidates per segment, at least
-constexpr int kMergeThreads = 256;
-constexpr int kMergeCap = 4096;           // entries one merge workgroup sorts
-constexpr int kMaxFan = 64;
+constexpr int kMergeThreads = 256;        // this file's own: a grid-stride over (row, output list), static LDS
+constexpr int kMergeCap = 4096;           // entries one merge workgroup sorts (the global merge sorts 8192 in dynamic LDS)
 constexpr int kMergeGrid = 8192;
-constexpr size_t kAlign = 256;
 
 static_assert(DGMI_ROW_TOPK_MAX_K <= kTrigger, "a row's list must fit below the sort trigger");
-
-// the per-row ranking key: logit descending, then candidate ascending
-__device__ __forceinline__ bool better(uint32_t fa, uint32_t ca, uint32_t fb, uint32_t cb) {
-  return fa > fb || (fa == fb && ca < cb);
-}
 
 // Bitonic sort, descending, of `rows` lists of n (a power of two) entries each, list r at r * stride_r of the SoA
 // arrays (f, c).  All threads of the block; ends with a barrier.
@@ -62,7 +50,7 @@ __device__ void rows_sort_desc(uint32_t* f, uint32_t* c, int rows, int stride_r,
         const bool desc = (lo & size) == 0;
         const int a = r * stride_r + lo, b = r * stride_r + hi;
         const uint32_t fl = f[a], fh = f[b], cl = c[a], ch = c[b];
-        if (better(fh, ch, fl, cl) == desc) {
+        if (RowKey::better(fh, ch, fl, cl) == desc) {
           f[a] = fh;
           f[b] = fl;
           c[a] = ch;
@@ -94,7 +82,7 @@ struct RowArgs {
 };
 
 __global__ __launch_bounds__(kThreads) void pair_mlp_row_topk_kernel(RowArgs a) {
-  __shared__ __attribute__((aligned(16))) float c_lds[kChunk * kCStride];
+  __shared__ __attribute__((aligned(16))) float c_lds[kChunk * kRowStride];
   __shared__ uint32_t ef[kRows * kRowCap], ec[kRows * kRowCap];
   __shared__ int s_used[kRows];
   __shared__ int s_need, s_max;
@@ -121,10 +109,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_row_topk_kernel(RowArgs a) 
     while (np < m) np <<= 1;
     for (int e = tid; e < kRows * np; e += kThreads) {
       const int r = e / np, p = e - r * np;
-      if (p >= s_used[r]) {
-        ef[r * kRowCap + p] = 0u;  // below every candidate: a real NaN pair has the same key but a smaller id
-        ec[r * kRowCap + p] = 0xffffffffu;
-      }
+      if (p >= s_used[r]) RowKey{ef, ec}.pad(r * kRowCap + p);
     }
     __syncthreads();
     rows_sort_desc(ef, ec, kRows, kRowCap, np, tid, kThreads);
@@ -143,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_row_topk_kernel(RowArgs a) 
   // offer the lane row's pair with candidate c; lanes 32..63 hold the same pairs and never append
   auto offer = [&](bool valid, float logit, uint32_t c) {
     const uint32_t f = order_key(logit);
-    if (half == 0 && valid && (!full || better(f, c, tf, tc))) {
+    if (half == 0 && valid && (!full || RowKey::better(f, c, tf, tc))) {
       const int pos = atomicAdd(&s_used[col], 1);
       if (pos < kRowCap) {  // always: at most 4 kSub appends per row between two checks
         rf[pos] = f;
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_row_topk_kernel(RowArgs a) 
       for (int e = tid; e < nc * 32; e += kThreads) {
         const int r = e >> 5, c4 = e & 31;
         const float4 v = *reinterpret_cast<const float4*>(a.C + (int64_t)(cc + r) * a.ldc + 4 * c4);
-        *reinterpret_cast<float4*>(c_lds + r * kCStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
+        *reinterpret_cast<float4*>(c_lds + r * kRowStride + 68 * (c4 >> 4) + 4 * (c4 & 15)) = v;
       }
       __syncthreads();
       const int lo = wave * kPerWave;
@@ -191,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void pair_mlp_row_topk_kernel(RowArgs a) 
           const uint32_t kwa = words ? bm[(int64_t)(cc + da) * a.nwords] : 0u;
           const uint32_t kwb = words ? bm[(int64_t)(cc + db) * a.nwords] : 0u;
           float la, lb;
-          score_two(c_lds + da * kCStride + 68 * half, c_lds + db * kCStride + 68 * half, x, dec, la, lb);
+          score_two(c_lds + da * kRowStride + 68 * half, c_lds + db * kRowStride + 68 * half, x, dec, la, lb);
           offer(row_ok && !((kwa >> col) & 1u), la, (uint32_t)(cc + da));
           offer(has_b && row_ok && !((kwb >> col) & 1u), lb, (uint32_t)(cc + db));
         }
@@ -249,8 +234,7 @@ __global__ __launch_bounds__(kMergeThreads) void row_merge_kernel(const uint32_t
         f[e] = in_f[src];
         c[e] = in_c[src];
       } else {
-        f[e] = 0u;
-        c[e] = 0xffffffffu;
+        RowKey{f, c}.pad(e);
       }
     }
     __syncthreads();
@@ -289,11 +273,9 @@ __global__ __launch_bounds__(256) void row_empty_kernel(int64_t n_query, int k, 
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 
-inline size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
 struct RowPlan {
-  int n_groups, n_seg, seg, grid, fan;
-  int64_t n_tasks, nwords;
+  SegmentPlan tasks;
+  int fan;
   size_t bitmap, parts_a, parts_b, total;  // byte offsets / size
 };
 
@@ -301,27 +283,13 @@ size_t parts_bytes(int64_t n_lists, int k) { return align_up((size_t)n_lists * (
 
 RowPlan make_row_plan(int64_t n_query, int64_t n_cand, int k) {
   RowPlan p;
-  p.n_groups = (int)((n_query + kRows - 1) / kRows);
-  // split the candidate axis until there are ~16 tasks per workgroup: all 50 000 diseases take 3 segments, a single
-  // query row takes 256
-  int64_t s = (kTaskTarget + p.n_groups - 1) / p.n_groups;
-  if (s > kMaxSeg) s = kMaxSeg;
-  if (s > (n_cand + kMinSeg - 1) / kMinSeg) s = (n_cand + kMinSeg - 1) / kMinSeg;
-  if (s < 1) s = 1;
-  p.seg = (int)((n_cand + s - 1) / s);
-  p.n_seg = (int)((n_cand + p.seg - 1) / p.seg);
-  p.n_tasks = (int64_t)p.n_groups * p.n_seg;
-  p.grid = (int)(p.n_tasks < kGrid ? p.n_tasks : kGrid);
-  int kp = 1;
-  while (kp < k) kp <<= 1;
-  p.fan = kMergeCap / kp;
-  if (p.fan > kMaxFan) p.fan = kMaxFan;
-  p.nwords = (n_query + 31) / 32;
+  p.tasks = segment_plan(n_query, n_cand, n_query);
+  p.fan = merge_fan(kMergeCap, k);
   p.bitmap = 0;
-  p.parts_a = align_up((size_t)n_cand * (size_t)p.nwords * 4);
-  p.parts_b = p.parts_a + parts_bytes(n_query * p.n_seg, k);
+  p.parts_a = bitmap_bytes(n_cand, p.tasks.nwords);
+  p.parts_b = p.parts_a + parts_bytes(n_query * p.tasks.n_seg, k);
   // a second list buffer only when a row's segment lists take more than one merge round
-  p.total = p.parts_b + (p.n_seg > p.fan ? parts_bytes(n_query * ((p.n_seg + p.fan - 1) / p.fan), k) : 0);
+  p.total = p.parts_b + (p.tasks.n_seg > p.fan ? parts_bytes(n_query * ((p.tasks.n_seg + p.fan - 1) / p.fan), k) : 0);
   return p;
 }
 
@@ -340,8 +308,6 @@ Parts parts_at(void* ws, size_t off, int64_t n_lists, int k) {
   return l;
 }
 
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 }  // namespace
 
 extern "C" {
@@ -357,53 +323,46 @@ DGMI_API int dgmi_pair_mlp_row_topk_f32(const float* X, int64_t ldx, int64_t n_q
                                         const int32_t* known_cand, int64_t n_known, int32_t k, int32_t* out_cand,
                                         float* out_logit, int32_t* out_count, int32_t* out_info, void* workspace,
                                         size_t workspace_bytes, dgmi_stream_t stream) {
-  if (h1 != kH1 || h2 != kH2 || k < 1 || k > DGMI_ROW_TOPK_MAX_K) return DGMI_ERR_INVALID_ARG;
-  if (n_query < 0 || n_cand < 0 || n_known < 0 || n_query > INT32_MAX || n_cand > INT32_MAX) return DGMI_ERR_INVALID_ARG;
+  if (!check_pair_extents(h1, h2, n_query, n_cand, n_known) || k < 1 || k > DGMI_ROW_TOPK_MAX_K) return DGMI_ERR_INVALID_ARG;
   if (n_query == 0) return DGMI_OK;
   if (out_cand == nullptr || out_logit == nullptr || out_count == nullptr || out_info == nullptr) return DGMI_ERR_INVALID_ARG;
-  if (n_known > 0 && (known_query == nullptr || known_cand == nullptr)) return DGMI_ERR_INVALID_ARG;
+  if (!check_known(known_query, known_cand, n_known)) return DGMI_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (n_cand == 0) {
+  if (n_cand == 0) {  // every row is empty, whatever the operands
     if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
     int64_t blocks = (n_query * k + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(row_empty_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n_query, (int)k, out_cand, out_logit,
                        out_count);
-    if (n_known > 0) {  // every known id is out of range: flag it, write nothing
-      int64_t kb = (n_known + 255) / 256;
-      if (kb > 4096) kb = 4096;
-      hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)kb), dim3(256), 0, s, known_cand, known_query, n_known, 0,
-                         (int)n_query, (int64_t)0, static_cast<uint32_t*>(nullptr), out_info);
-    }
+    // every known id is out of range: flag it
+    if (n_known > 0 && build_known_bitmap(known_cand, known_query, n_known, 0, n_query, 0, nullptr, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
     return hipGetLastError() == hipSuccess ? DGMI_OK : DGMI_ERR_LAUNCH;
   }
-  if (X == nullptr || C == nullptr || W2 == nullptr || b2 == nullptr || w3 == nullptr || b3 == nullptr) return DGMI_ERR_INVALID_ARG;
-  if (ldx < kH1 || ldc < kH1 || ldx % 4 != 0 || ldc % 4 != 0 || misaligned(X) || misaligned(C) || misaligned(W2))
-    return DGMI_ERR_INVALID_ARG;
+  if (!check_pair_operands(X, ldx, C, ldc, W2, b2, w3, b3)) return DGMI_ERR_INVALID_ARG;
   const RowPlan plan = make_row_plan(n_query, n_cand, k);
+  const SegmentPlan& tasks = plan.tasks;
   if (workspace == nullptr || workspace_bytes < plan.total) return DGMI_ERR_WORKSPACE;
 
   if (hipMemsetAsync(out_info, 0, 2 * sizeof(int32_t), s) != hipSuccess) return DGMI_ERR_LAUNCH;
   uint32_t* bitmap = nullptr;
   if (n_known > 0) {
     bitmap = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + plan.bitmap);
-    if (hipMemsetAsync(bitmap, 0, (size_t)n_cand * (size_t)plan.nwords * 4, s) != hipSuccess) return DGMI_ERR_LAUNCH;
-    int64_t blocks = (n_known + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(known_bitmap_kernel, dim3((unsigned)blocks), dim3(256), 0, s, known_cand, known_query, n_known,
-                       (int)n_cand, (int)n_query, plan.nwords, bitmap, out_info);
+    if (build_known_bitmap(known_cand, known_query, n_known, n_cand, n_query, tasks.nwords, bitmap, out_info, s) != hipSuccess)
+      return DGMI_ERR_LAUNCH;
   }
 
-  const Parts pa = parts_at(workspace, plan.parts_a, n_query * plan.n_seg, k);
-  RowArgs args{X, ldx, C, ldc, (int)n_query, (int)n_cand, W2, b2, w3, b3, bitmap, plan.nwords, k, plan.n_groups,
-               plan.n_seg, plan.seg, plan.n_tasks, pa.f, pa.c, pa.n};
-  hipLaunchKernelGGL(pair_mlp_row_topk_kernel, dim3((unsigned)plan.grid), dim3(kThreads), 0, s, args);
+  const Parts pa = parts_at(workspace, plan.parts_a, n_query * tasks.n_seg, k);
+  RowArgs args{X, ldx, C, ldc, (int)n_query, (int)n_cand, W2, b2, w3, b3, bitmap, tasks.nwords, k, tasks.n_groups,
+               tasks.n_seg, tasks.seg, tasks.n_tasks, pa.f, pa.c, pa.n};
+  hipLaunchKernelGGL(pair_mlp_row_topk_kernel, dim3((unsigned)tasks.grid), dim3(kThreads), 0, s, args);
   if (hipGetLastError() != hipSuccess) return DGMI_ERR_LAUNCH;
 
   // rounds: lists A -> B -> A ... until each row's lists are one, written as the result
-  const int64_t n_b = (plan.n_seg + plan.fan - 1) / plan.fan;
-  const Parts pb = plan.n_seg > plan.fan ? parts_at(workspace, plan.parts_b, n_query * n_b, k) : Parts{nullptr, nullptr, nullptr};
-  int n_in = plan.n_seg;
+  const int64_t n_b = (tasks.n_seg + plan.fan - 1) / plan.fan;
+  const Parts pb = plan.tasks.n_seg > plan.fan ? parts_at(workspace, plan.parts_b, n_query * n_b, k)
+                                          : Parts{nullptr, nullptr, nullptr};
+  int n_in = tasks.n_seg;
   bool in_a = true;
   for (;;) {
     const int n_out = (n_in + plan.fan - 1) / plan.fan;

@@ -37,7 +37,7 @@ def expected_ranks(L, known, pair_q, pair_c):
 
 
 def given_plan(n_query, n_cand, n_pairs):
-    """``(n_groups, n_seg, seg, workspace_bytes)`` of a rank_list call (csrc/dgmi_pairs_given.hip make_given_plan): the
+    """``(n_groups, n_seg, seg, workspace_bytes)`` of a rank_list call (csrc/dgmi_pair_stream.h segment_plan): the
     listed pairs go in groups of 32, the candidate axis is cut into ``n_seg`` segments of ``seg`` candidates (the last
     one shorter) so that there are about 16 tasks per workgroup, and a pair's result is the sum over its segments.  A
     workgroup streams a segment in chunks of 128 candidates; of a chunk of n its four waves take ``2 * ceil(n / 8)``
