@@ -148,7 +148,9 @@ __global__ __launch_bounds__(kThreads) void knn_cosine_topk_kernel(const float* 
         }
       }
       if (gridDim.y == 1) {
-        nbr[(int64_t)(q0 + tid) * k + out] = list_idx[at];  // k <= N: the 8 lists hold at least k real entries
+        // k <= N: the 8 lists hold at least k real entries — unless rows hold a NaN: `s > thr` never takes a NaN score, so
+        // with fewer than k comparable rows the unfilled (-inf, -1) entries come last, and a NaN query's list is k times -1
+        nbr[(int64_t)(q0 + tid) * k + out] = list_idx[at];
       } else {
         const int64_t o = ((int64_t)blockIdx.y * N + (q0 + tid)) * k + out;
         part_val[o] = which >= 0 ? best : -INFINITY;

@@ -76,6 +76,8 @@ constexpr int kScreenMinRows = 1536;  // measured crossover against the fp32 ker
 constexpr float kScreenEps = 0.008f;
 constexpr float kUnset = -2.0f;                      // below every cosine; list filler
 constexpr float kMasked = -4.0f;                     // score given to padding candidates
+constexpr float kNoScore = -3.0e38f;                 // what a NaN score becomes in wave_topk_insert: below every entry, kMasked included
+constexpr float kDeadBelow = -3.0f;                  // between kMasked and the lowest emission threshold, kUnset - 2 eps
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -91,7 +93,10 @@ __global__ __launch_bounds__(256) void knn_to_bf16_kernel(const float* __restric
   for (int j = 0; j < 8; ++j) {
     const float f = row < N && c0 + j < D ? Xn[(int64_t)row * ld + c0 + j] : 0.f;
     const uint32_t u = __float_as_uint(f);
-    h[j] = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;  // round to nearest even (inputs are finite, |x| <= 1)
+    h[j] = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;  // round to nearest even
+    // a NaN stays a NaN (the rounding carry would turn payloads into Inf, -0 or 0): every approx score of its row is then
+    // NaN, which no comparison of the screen accepts — the row is offered to nobody and is offered nothing
+    if ((u & 0x7fffffffu) > 0x7f800000u) h[j] = 0x7fc0u;
   }
   uint4 o;
   o.x = h[0] | (h[1] << 16);
@@ -337,10 +342,14 @@ __global__ __launch_bounds__(Shape<BIG>::kThreads, 2) void knn_screen_kernel(Scr
           for (int cs = 0; cs < 2; ++cs)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
+              // Branch-free sorted insert, lowest first: the new top[i] is the median of (top[i - 1], top[i], s).  A NaN score
+              // (a NaN row) is no candidate and changes nothing: `v_med3_f32` with a NaN operand returns the minimum of the
+              // other two, top[i], and fmaxf(top[0], NaN) = top[0].  (The first form, fmaxf(top[i], fminf(top[i - 1], s)), is
+              // two instructions a step, and fminf(top[i - 1], NaN) = top[i - 1] entered top[0] a second time: tau' above tau.)
               const float s = acc[qs][cs][v];
-              top[qs][3] = fmaxf(top[qs][3], fminf(top[qs][2], s));  // branch-free sorted insert, lowest first
-              top[qs][2] = fmaxf(top[qs][2], fminf(top[qs][1], s));
-              top[qs][1] = fmaxf(top[qs][1], fminf(top[qs][0], s));
+              top[qs][3] = __builtin_amdgcn_fmed3f(top[qs][2], top[qs][3], s);
+              top[qs][2] = __builtin_amdgcn_fmed3f(top[qs][1], top[qs][2], s);
+              top[qs][1] = __builtin_amdgcn_fmed3f(top[qs][0], top[qs][1], s);
               top[qs][0] = fmaxf(top[qs][0], s);
             }
         }
@@ -610,10 +619,10 @@ __device__ __forceinline__ void screen8_quadrant(floatx4 (&acc)[8][4], float (&t
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float s = acc[nt][2 * CQ + m][j];
-            top[nt][3] = fmaxf(top[nt][3], fminf(top[nt][2], s));  // branch-free sorted insert, lowest first
-            top[nt][2] = fmaxf(top[nt][2], fminf(top[nt][1], s));
-            top[nt][1] = fmaxf(top[nt][1], fminf(top[nt][0], s));
+            const float s = acc[nt][2 * CQ + m][j];  // (median insert, a NaN score changes nothing: see knn_screen_kernel)
+            top[nt][3] = __builtin_amdgcn_fmed3f(top[nt][2], top[nt][3], s);
+            top[nt][2] = __builtin_amdgcn_fmed3f(top[nt][1], top[nt][2], s);
+            top[nt][1] = __builtin_amdgcn_fmed3f(top[nt][0], top[nt][1], s);
             top[nt][0] = fmaxf(top[nt][0], s);
           }
       }
@@ -985,7 +994,10 @@ __global__ __launch_bounds__(256) void knn_tau_kernel(const float* __restrict__ 
 }
 
 // A wave's running top-k: lane i < k holds the i-th best (score desc, id asc).  Every lane passes the same (s, cid).
+// Unfilled entries are (kMasked, -1).  A NaN score is no candidate: fmaxf(NaN, kNoScore) = kNoScore, which every entry beats
+// (pos = k, nothing moves); left as it is `better` would be false on every lane: first place.
 __device__ __forceinline__ void wave_topk_insert(float& best_s, int32_t& best_id, float s, int32_t cid, int k, int lane) {
+  s = fmaxf(s, kNoScore);
   const bool better = best_s > s || (best_s == s && best_id < cid);
   const int pos = __popcll(__ballot(better && lane < k));
   const float up_s = __shfl_up(best_s, 1);
@@ -1049,8 +1061,11 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
     return;
   }
   if (lane == 0) flags[q] = 0;
+  // Fewer than k live entries (fewer than k comparable rows; none at all for a query row that holds a NaN): tau falls to the dead
+  // slots' kMasked.  keep_from stops at kDeadBelow, between the two: every live entry is rescored (its score reached an emission
+  // threshold, and those are >= kUnset - 2 eps) and no dead one — a dead slot has no row (id -1), `wave_dot` would read in front of Xn
   const float tau = kJ >= 64 ? wave_kth_largest_bisect<kJ>(work, k) : wave_kth_largest<kJ>(work, k, lane);
-  const float keep_from = tau - 2.f * kScreenEps;
+  const float keep_from = fmaxf(tau - 2.f * kScreenEps, kDeadBelow);
 
   // the query row, 16 B per lane per 256 columns
   const int d4 = D / 4;
@@ -1060,7 +1075,7 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float* __restric
   for (int i = 0; i < 4; ++i) qv[i] = lane + 64 * i < d4 ? qrow[lane + 64 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
 
   float best_s = kMasked;  // lane i < k: the i-th best (score desc, id asc)
-  int32_t best_id = 0x7fffffff;
+  int32_t best_id = -1;    // unfilled: fewer than k comparable rows
   if constexpr (kJ < 64) {
     // short buffers (k <= 8; k <= 16 on the full rectangle): few registers, many waves per SIMD — they hide the latency of one
     // entry after the other (batched like the long ones this pass went 0.56 -> 0.90 ms at N = 100 000, k = 4)
@@ -1140,7 +1155,7 @@ __global__ __launch_bounds__(256) void knn_exact_rows_kernel(const float* __rest
 #pragma unroll
   for (int i = 0; i < 4; ++i) qv[i] = lane + 64 * i < d4 ? qrow[lane + 64 * i] : make_float4(0.f, 0.f, 0.f, 0.f);
   float best_s = kMasked;
-  int32_t best_id = 0x7fffffff;
+  int32_t best_id = -1;  // unfilled, as in the rescoring
   for (int c = wave; c < N; c += 4) wave_topk_insert(best_s, best_id, wave_dot(qv, Xn + (int64_t)c * ld, d4, lane), c, k, lane);
   m_s[wave * 64 + lane] = best_s;
   m_id[wave * 64 + lane] = best_id;

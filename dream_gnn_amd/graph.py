@@ -826,9 +826,19 @@ def feature_similarity_graph(features: torch.Tensor, k: int, symm: bool = True,
     a bf16-MFMA screen with exact fp32 rescoring from 1536 rows (1.5x / 13x the torch path at
     N = 763 / 100 000); otherwise, or with ``fused=False``, a row-blocked torch GEMM +
     top-k (an 8192-row block against 100k columns is 3.3 GB of fp32, reduced to k ids per row at
-    once).  ``fused=True`` insists on the kernel."""
+    once).  ``fused=True`` insists on the kernel.
+
+    Raises ``ValueError`` when a feature row holds a NaN or an infinity, before any kernel runs (one readback; the
+    builder runs once per fold).  A deviation from the reference, which builds a meaningless graph from such rows without
+    a word (``argpartition`` puts NaN last); it is also why a ``-1`` of ``ops.knn_cosine_topk`` never reaches the adjacency,
+    which later products gather from without a range check."""
     n = features.shape[0]
     k_actual = min(k, n - 1)
+    bad_rows = ~torch.isfinite(features).reshape(n, -1).all(dim=1)
+    n_bad = int(bad_rows.sum())  # the one readback
+    if n_bad:
+        raise ValueError("feature_similarity_graph: %d of %d feature rows hold a NaN or an infinity (first ids: %s)"
+                         % (n_bad, n, ", ".join(str(i) for i in bad_rows.nonzero().reshape(-1)[:8].tolist())))
     norms = features.norm(dim=1, keepdim=True)
     norms = torch.where(norms == 0, torch.full_like(norms, 1e-10), norms)  # data_loader.py:334-335
     xn = features / norms

@@ -1291,7 +1291,14 @@ def knn_cosine_supported(N: int, D: int, k: int) -> bool:
 def knn_cosine_topk(xn: torch.Tensor, k: int) -> torch.Tensor:
     """``(N, k)`` int32 ids of the k largest cosine similarities per row of the row-normalised ``xn``
     (self included, descending) — ``dgmi_knn_cosine_topk_f32``: fp32-MFMA similarity tiles reduced to
-    a running top-k on chip."""
+    a running top-k on chip.
+
+    Non-finite rows (``include/dgmi.h``): a row that holds a NaN is in no other row's list and its own list is ``k``
+    times ``-1``; a finite row's list is its top ``min(k, #finite rows)`` finite rows followed by ``-1`` (the only
+    filler), the same rows the call returns on the finite rows alone; rows with ``+-inf`` elements get valid-or-``-1``
+    distinct ids in unspecified order.  No bit pattern in ``xn`` makes the search read or write outside ``xn``, the
+    result and its workspace.  The call does not synchronise and does not look at the lists: a caller that gathers with
+    them checks for ``-1`` first (``graph.feature_similarity_graph`` refuses non-finite features before it calls)."""
     _require_device(xn)
     return _T.knn_cosine_topk(xn, int(k))
 

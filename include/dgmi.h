@@ -391,6 +391,18 @@ DGMI_API int dgmi_compact_layout_i32(const int32_t* ptr, int64_t n_ptr, const in
  * (rows must be unit vectors or zero for that bound).  A zero row has similarity 0 to every row, itself
  * included, so its list is the usual top-k of a row of zeros and its own id is not necessarily first (or
  * present).  Ties at the k-th value are broken arbitrarily (upstream too).
+ * Non-finite rows:
+ *  - a row that holds a NaN is comparable with nothing: it appears in no other row's list, and its own list is
+ *    k times -1;
+ *  - a finite row's list is the top k_f = min(k, #finite rows) finite rows (self included) by similarity
+ *    descending, followed by k - k_f entries of -1; -1 is the only filler, on every path;
+ *  - the lists of the finite rows of a table that also holds NaN rows are those the same call returns on the
+ *    finite rows alone, up to the renumbering of the ids: a NaN candidate changes no threshold, flag or list;
+ *  - rows with +-Inf elements and no NaN get address safety only: every id is in [0, N) or -1, the non-negative ids
+ *    of a list are distinct, nothing outside nbr and the workspace is written; the order is unspecified;
+ *  - for any bit pattern in Xn no kernel of the search reads or writes outside Xn[0 : N * ld], nbr and the workspace.
+ * Rows that are finite but not unit vectors (or zero) stay out of contract for the ORDER from 1536 rows on (the screen's
+ * margin assumes |q| |c| <= 1); the address promise covers them.
  * dgmi_knn_cosine_supported: 1 if the shape fits the kernels (D % 8 == 0, k <= N, k <= 16 — or k <= 64 when
  * N >= 1536 and D <= 1024, where the bf16 screen runs and a wave's lanes hold the top-k —, the 32-query
  * tile + lists within LDS: D <= 1024 for k <= 4, D <= 896 for k = 16); callers fall back otherwise.

@@ -15,9 +15,9 @@ ENTRY_POINTS = ["dgmi_rows_to_bf16", "dgmi_spmm_sliced_bf16"]
 # sha256 of the pinned headers: the bf16 entry points were added WITHOUT touching them (dgmi.h: re-pinned after one comment
 # sentence on finite edge weights was added to the edge-dropout paragraph, and again after one on zero rows was added to the
 # kNN paragraph, and again after one on the key bits `dgmi_csr_sliced_from_csr_i32` admits, and again after one on the NaN-keeping relu
-# of `dgmi_gather_add_f32`; no declaration changed)
+# of `dgmi_gather_add_f32`, and again after the non-finite contract was added to the kNN paragraph; no declaration changed)
 PINNED = {
-    "dgmi.h": "d5cc15dd209208be633627b8ca243b8a6a3bf735dfc87f55e2449514c3e4aad4",
+    "dgmi.h": "07cc4abb82fbd1fd66b8a314ac613af6ced1cf9f4ef487dea9e480a56148c306",
     "dgmi_pairs.h": "9911f584a90f5b340c7d3cfe009e71d17b431dedc7f3817f687c6c4ef2b3ca4f",
     "dgmi_rank.h": "d7333eb8cf8e95e9bbaa5ad2e7ffced95ebc89617e249009e25988cf854da931",
     "dgmi_above.h": "76600e1650a703f70f44f841706e331aa9871f7f18cf07ca3bf4a0b7a5595aea",
