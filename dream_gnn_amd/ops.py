@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import operator
 import os
 import threading
 from typing import Optional, Tuple
@@ -400,11 +401,36 @@ def _table_cap(tiers, degree: float) -> int:
     return cap
 
 
+class _Direction:
+    """One direction of a structure — the rows a product writes and the columns it gathers: the forward product
+    (rows = destinations) or the transposed one (rows = sources; its CSR is built by the first use,
+    :meth:`CSRGraph._built`).  Everything a product reads per direction, so that it is written once for both."""
+
+    __slots__ = ("transposed", "suffix", "csr_key", "sliced_key", "split_key", "gathered_name", "out_name",
+                 "n_rows", "n_cols", "cols_coo", "indptr", "indices", "eid", "plan", "max_deg", "regular", "sliced", "split")
+
+    def __init__(self, suffix, n_rows, n_cols, cols_coo, regular, gathered_name, out_name):
+        self.transposed, self.suffix = bool(suffix), suffix  # suffix of this direction's keys in a view's _v / _c
+        self.csr_key, self.sliced_key, self.split_key = "csr" + suffix, "sliced" + suffix, "split" + suffix
+        self.gathered_name, self.out_name = gathered_name, out_name  # how errors call the scales of the gathered / the output rows
+        self.n_rows, self.n_cols, self.cols_coo = n_rows, n_cols, cols_coo  # cols_coo: the gathered ids in the caller's edge order
+        self.indptr = self.indices = self.eid = self.plan = None
+        self.max_deg = None  # longest row, once a readback has told
+        self.regular = regular  # no row is extremely long (None: not known yet, CSRGraph._decide_regular)
+        self.sliced = self.split = None  # the first XCD-sliced layout (others: _Structure.wide) and the split form
+
+
 class _Structure:
     """Everything about a CSRGraph that depends on the edge list only (shared by value views)."""
 
-    __slots__ = ("n_dst", "n_src", "dst", "src", "indptr", "indices", "eid", "plan", "planned", "t",
-                 "sliced", "sliced_t", "wide", "regular", "regular_t", "validated", "split", "split_t", "max_deg", "max_deg_t")
+    __slots__ = ("n_dst", "n_src", "dst", "src", "nnz", "planned", "validated", "wide", "fwd", "bwd")
+
+
+# the per-direction state under the names it had as loose slots: indptr .. split read the forward record, *_t the transposed
+for _side, _sfx, _fields in (("fwd", "", ("indptr", "indices", "eid", "plan", "max_deg", "regular", "sliced", "split")),
+                             ("bwd", "_t", ("max_deg", "regular", "sliced", "split"))):
+    for _f in _fields:
+        setattr(_Structure, _f + _sfx, property(operator.attrgetter(_side + "." + _f)))
 
 
 # Rows longer than this are cut into virtual rows before the XCD-local kernel sees them (power-law
@@ -543,11 +569,8 @@ class CSRGraph:
         S.src = src.to(torch.int32).contiguous()
         if vals is not None and vals.shape[0] != S.dst.shape[0]:
             raise RuntimeError("vals/edge-list length mismatch")
-        S.indptr, S.indices, S.eid, flag = csr_from_coo(S.dst, S.src, S.n_dst, S.n_src, return_flag=True)
         S.planned = planned
-        S.t = S.sliced = S.sliced_t = S.split = S.split_t = None
         S.wide = {}  # (transposed, n_slices) -> an XCD-sliced layout of another slice count than sliced / sliced_t have (_layout_of)
-        S.max_deg = S.max_deg_t = None  # longest row of the CSR / of the transposed CSR, once a readback has told
         S.validated = bool(check_range)
         # `regular`: no destination row is extremely long, so the XCD-local kernel (which walks a
         # (row, slice) segment sequentially) is safe to use.  Known after the one readback of a validated build
@@ -556,15 +579,17 @@ class CSRGraph:
         # per-step graphs of the real datasets and never inside a stream capture.  (Until round 4 unchecked builds were
         # simply "not regular": every adjacency built by graph.similarity_graph / feature_similarity_graph — trusted by
         # construction — ran the planned kernel at scale, 0.84 ms against 0.41 ms per kNN-64 product.)
-        S.regular = bool(regular) if regular is not None else None
-        S.regular_t = regular_t
+        D = S.fwd = _Direction("", S.n_dst, S.n_src, S.src, bool(regular) if regular is not None else None, "src_scale", "dst_scale")
+        S.bwd = _Direction("_t", S.n_src, S.n_dst, S.dst, regular_t, "dst_scale", "src_scale")  # its CSR: _built, on first use
+        D.indptr, D.indices, D.eid, flag = csr_from_coo(S.dst, S.src, S.n_dst, S.n_src, return_flag=True)
+        S.nnz = int(D.indices.shape[0])
         self._set_values(None if vals is None else vals.to(torch.float32).contiguous())
         if check_range:
             # ids are checked BEFORE anything is derived from the CSR: the sort of an edge list with
             # ids outside [0, n) leaves indptr in bounds but meaningless, and a launch plan built
             # from it would be garbage (the plan kernels clamp, the product would still be wrong)
             self._validate(flag)
-        S.plan = build_plan(S.indptr, int(S.indices.shape[0])) if planned else None
+        D.plan = build_plan(D.indptr, S.nnz) if planned else None
 
     # -- values -----------------------------------------------------------------------------------
     def _set_values(self, coo_vals, keep=None):
@@ -667,20 +692,15 @@ class CSRGraph:
         if m is None:
             if self._capturing():
                 return None  # the decision needs a readback: not inside a capture (the value stream is always right)
-            S = self._S
             m = False
-            scale, code, fail = _T.row_multiplicity(S.indptr, self.vals, MULT_REL_TOL)
-            if int(fail.item()) == 0:
-                code_coo = torch.empty_like(code)
-                code_coo[S.eid.long()] = code
-                m = ("row", scale, code_coo)
-            else:
-                indptr_t, _, vals_t, _ = self.transposed()
-                scale, code, fail = _T.row_multiplicity(indptr_t, vals_t, MULT_REL_TOL)
+            for kind, D in (("row", self._S.fwd), ("col", self._S.bwd)):  # the transposed CSR is built only if "row" fails
+                D = self._built(D)
+                scale, code, fail = _T.row_multiplicity(D.indptr, self._vals_for(D.csr_key, D.eid), MULT_REL_TOL)
                 if int(fail.item()) == 0:
                     code_coo = torch.empty_like(code)
-                    code_coo[S.t[2].long()] = code
-                    m = ("col", scale, code_coo)
+                    code_coo[D.eid.long()] = code
+                    m = (kind, scale, code_coo)
+                    break
             self._v["mult"] = m
         return m or None
 
@@ -730,15 +750,15 @@ class CSRGraph:
     @property
     def vals(self):
         """Edge values in CSR order (None for an unweighted graph)."""
-        return self._vals_for("csr", self._S.eid)
+        return self._vals_for("csr", self._S.fwd.eid)
 
     @property
     def nnz(self) -> int:
-        return int(self._S.indices.shape[0])
+        return self._S.nnz
 
     @property
     def device(self):
-        return self._S.indptr.device
+        return self._S.fwd.indptr.device
 
     @staticmethod
     def _is_regular(max_deg: int, nnz: int, n_rows: int) -> bool:
@@ -748,38 +768,33 @@ class CSRGraph:
 
     def _validate(self, flag: torch.Tensor):
         """One host sync: the range flag of the device COO->CSR and the maximum in-degree."""
-        S = self._S
+        S, D = self._S, self._S.fwd
         if self.nnz == 0:
-            S.regular = True
+            D.regular = True
             return
-        bad, max_deg = torch.stack([flag.reshape(()), (S.indptr[1:] - S.indptr[:-1]).max()]).tolist()
+        bad, max_deg = torch.stack([flag.reshape(()), (D.indptr[1:] - D.indptr[:-1]).max()]).tolist()
         if bad:  # error path only: say which side and by how much
             dlo, dhi, slo, shi = (int(v) for v in torch.stack([S.dst.min(), S.dst.max(), S.src.min(), S.src.max()]).tolist())
             if dlo < 0 or dhi >= S.n_dst:
                 raise RuntimeError("destination id out of range [0, %d): min %d max %d" % (S.n_dst, dlo, dhi))
             raise RuntimeError("source id out of range [0, %d): min %d max %d" % (S.n_src, slo, shi))
-        S.max_deg = int(max_deg)
-        S.regular = self._is_regular(int(max_deg), self.nnz, S.n_dst)
+        D.max_deg = int(max_deg)
+        D.regular = self._is_regular(int(max_deg), self.nnz, S.n_dst)
 
     @staticmethod
     def _capturing() -> bool:
         return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
-    def _decide_regular(self, X, transposed: bool):
-        """Settle ``regular`` / ``regular_t`` of an unchecked build when a product large enough to care arrives."""
-        S = self._S
-        n_cols = S.n_dst if transposed else S.n_src
-        small = X.dim() != 2 or n_cols * X.shape[1] * 4 < min(SLICED_MIN_TABLE_BYTES, SPLIT_MIN_TABLE_BYTES)
+    def _decide_regular(self, X, D: _Direction):
+        """Settle ``regular`` of direction ``D`` of an unchecked build when a product large enough to care arrives."""
+        small = X.dim() != 2 or D.n_cols * X.shape[1] * 4 < min(SLICED_MIN_TABLE_BYTES, SPLIT_MIN_TABLE_BYTES)
         # a VALIDATED build has synchronised once already and reads the transposed graph's longest row back whatever the
         # size (it also tells whether the planned form's second launch can be skipped: _plan_if_needed)
-        if (small and not S.validated) or not X.is_cuda or self._capturing():
+        if (small and not self._S.validated) or not X.is_cuda or self._capturing():
             return  # stays unknown (treated as "not regular" for this product): small tables never take the sliced form
-        indptr = self._t_struct()[0] if transposed else S.indptr
-        max_deg = int((indptr[1:] - indptr[:-1]).max()) if self.nnz else 0
-        if transposed:
-            S.max_deg_t, S.regular_t = max_deg, self._is_regular(max_deg, self.nnz, S.n_src)
-        else:
-            S.max_deg, S.regular = max_deg, self._is_regular(max_deg, self.nnz, S.n_dst)
+        indptr = self._built(D).indptr
+        D.max_deg = int((indptr[1:] - indptr[:-1]).max()) if self.nnz else 0
+        D.regular = self._is_regular(D.max_deg, self.nnz, D.n_rows)
 
     def _use_sliced(self, F: int, n_rows: int, n_cols: int, regular: bool) -> bool:
         if FORCE_KERNEL is not None:  # debugging / A-B aid: DGMI_FORCE_KERNEL=planned|sliced
@@ -831,93 +846,71 @@ class CSRGraph:
             return None
         return plan
 
+    def _built(self, D: _Direction) -> _Direction:
+        """``D`` with its CSR (and plan) in place: the transposed direction's is made by its first use."""
+        if D.indptr is None:
+            S = self._S
+            D.indptr, D.indices, D.eid = csr_from_coo(S.src, S.dst, S.n_src)
+            D.plan = build_plan(D.indptr, S.nnz) if S.planned else None
+        return D
+
     def _t_struct(self):
-        S = self._S
-        if S.t is None:
-            indptr_t, indices_t, eid_t = csr_from_coo(S.src, S.dst, S.n_src)
-            S.t = (indptr_t, indices_t, eid_t, build_plan(indptr_t, self.nnz) if S.planned else None)
-        return S.t
+        T = self._built(self._S.bwd)
+        return T.indptr, T.indices, T.eid, T.plan
 
     def transposed(self):
         """(indptr_t, indices_t, vals_t, plan_t): CSR of the reversed edges, rows = source nodes."""
-        indptr_t, indices_t, eid_t, plan_t = self._t_struct()
-        return indptr_t, indices_t, self._vals_for("csr_t", eid_t), plan_t
+        T = self._built(self._S.bwd)
+        return T.indptr, T.indices, self._vals_for(T.csr_key, T.eid), T.plan
 
-    def _run(self, indptr, indices, vals, plan, n_rows, n_cols, X, col_scale, row_scale, out, eid=None, epi=None):
-        dev = indptr.device
+    def _run(self, D: _Direction, X, col_scale, row_scale, out, epi):
+        """The planned or (no plan, or no row longer than its chunk) the wave-per-row product of direction ``D``."""
+        dev = D.indptr.device
         if not X.is_cuda or X.device != dev:
-            _require_device(indptr, X)
-        if X.dim() == 2 and X.shape[0] != n_cols:
-            raise RuntimeError("X has %d rows, the graph has %d source nodes" % (X.shape[0], n_cols))
-        return _launch_spmm(dev, indptr, indices, vals, X, None if col_scale is None else col_scale.reshape(-1),
-                            None if row_scale is None else row_scale.reshape(-1), out, plan, n_rows, n_cols, 0, 0,
-                            eid if self._keep is not None else None, self._keep, epi)
+            _require_device(D.indptr, X)
+        if X.dim() == 2 and X.shape[0] != D.n_cols:
+            raise RuntimeError("X has %d rows, the graph has %d source nodes" % (X.shape[0], D.n_cols))
+        return _launch_spmm(dev, D.indptr, D.indices, self._vals_for(D.csr_key, D.eid), X,
+                            None if col_scale is None else col_scale.reshape(-1),
+                            None if row_scale is None else row_scale.reshape(-1), out, self._plan_if_needed(D.plan, D.max_deg),
+                            D.n_rows, D.n_cols, 0, 0, D.eid if self._keep is not None else None, self._keep, epi)
 
     # -- bf16 gather (DESIGN §4.12) ------------------------------------------------------------------
-    def _bf16_gather_reason(self, F: int, transposed: bool) -> Optional[str]:
-        """None when a product of width ``F`` gathers bf16 on request, else why it does not.  The form rule
-        (``_use_sliced``) keeps judging the FLOAT32 table bytes: its thresholds were fitted to 4-byte rows."""
-        S = self._S
-        n_rows, n_cols, regular = (S.n_src, S.n_dst, S.regular_t) if transposed else (S.n_dst, S.n_src, S.regular)
+    def _bf16_gather_reason(self, F: int, D: _Direction) -> Optional[str]:
+        """None when a product of width ``F`` in direction ``D`` gathers bf16 on request, else why it does not.  The form
+        rule (``_use_sliced``) keeps judging the FLOAT32 table bytes: its thresholds were fitted to 4-byte rows."""
         if F % 8 != 0:
             return "F = %d is not a multiple of 8 (a lane loads 8 bf16 columns)" % F
-        if (bool(regular) and self._few_long_rows(F, n_rows, n_cols)) or not self._use_sliced(F, n_rows, n_cols, regular):
+        if (bool(D.regular) and self._few_long_rows(F, D.n_rows, D.n_cols)) or not self._use_sliced(F, D.n_rows, D.n_cols, D.regular):
             return ("a %d x %d product at F = %d does not take the plain XCD-local form (it runs the planned, wave-per-row "
-                    "or split kernels, which gather float32 only)" % (n_rows, n_cols, F))
+                    "or split kernels, which gather float32 only)" % (D.n_rows, D.n_cols, F))
         return None
 
     def takes_bf16_gather(self, F: int, transposed: bool = False) -> bool:
         """Whether ``spmm`` (``transposed=True``: ``spmm_t``) honours ``gather_dtype=torch.bfloat16`` at width ``F``:
         the product takes the plain XCD-local form and ``F % 8 == 0``.  Otherwise a float32 ``X`` silently takes the
         float32 path and a bfloat16 ``X`` raises."""
-        S = self._S
-        if (S.regular_t if transposed else S.regular) is None:
-            self._decide_regular(torch.empty((0, int(F)), dtype=torch.float32, device=self.device), transposed)
-        return self._bf16_gather_reason(int(F), transposed) is None
+        D = self._S.bwd if transposed else self._S.fwd
+        if D.regular is None:
+            self._decide_regular(torch.empty((0, int(F)), dtype=torch.float32, device=self.device), D)
+        return self._bf16_gather_reason(int(F), D) is None
 
-    def _bf16_request(self, X, out, gather_dtype, transposed: bool) -> bool:
-        """True: run :meth:`_spmm_bf16`.  False: today's float32 path.  Raises for a bfloat16 ``X`` that cannot be gathered."""
+    def _bf16_request(self, X, out, gather_dtype, D: _Direction) -> bool:
+        """True: gather bf16 on the plain XCD-local form.  False: the float32 product.  Raises for a bfloat16 ``X`` that
+        cannot be gathered."""
         if X.dtype != torch.bfloat16 and _resolve_gather_dtype(gather_dtype) != torch.bfloat16:
             return False
         if X.dim() != 2:
             reason = "X is not 2-D"
         else:
-            reason = self._bf16_gather_reason(X.shape[1], transposed)
+            reason = self._bf16_gather_reason(X.shape[1], D)
             if reason is None and not _sliced_bf16_ok(X, out):
                 reason = "the rows of X (or out) are not contiguous and 16-byte aligned"
         if reason is not None and X.dtype == torch.bfloat16:
             raise RuntimeError("a bfloat16 X is only taken by the XCD-local bf16 gather, and %s: pass the float32 table" % reason)
         return reason is None
 
-    def _spmm_bf16(self, X, gathered_scale, out_scale, out, epi, transposed: bool):
-        """The plain XCD-local product with a bf16 gather: ``gathered_scale`` multiplies the gathered rows (folded into
-        the conversion of a float32 ``X``), ``out_scale`` the output rows (applied by the plane reduce)."""
-        S = self._S
-        name, layout = self._layout_of(transposed)  # the pair's 8 slices: the library runs its owned form on them where it wins (DESIGN §4.12)
-        mult = self._mult_ids(name, layout)
-        if mult is not None:  # the scale of `scale x multiplicity` values lands on the output rows or on the gathered rows
-            if (mult[0] == "row") != transposed:
-                out_scale = self._fold(mult[1], out_scale)
-            else:
-                gathered_scale = self._fold(mult[1], gathered_scale)
-        if X.dtype == torch.bfloat16:
-            if gathered_scale is not None:
-                raise RuntimeError("a bfloat16 X cannot take a scale on the gathered rows (src_scale, or the row scale of this "
-                                   "graph's `scale x multiplicity` values): it is applied in float32 before the one rounding — "
-                                   "pass the float32 table")
-            gd = None
-        else:
-            gd = torch.bfloat16
-        c = self._compacted(name, layout, mult)
-        if c is not None:
-            return c.spmm(X, gathered_scale, out_scale, out, epi=epi, gather_dtype=gd)
-        if mult is not None:
-            return layout.spmm(X, gathered_scale, out_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2],
-                               id_mult=True, gather_dtype=gd)
-        return layout.spmm(X, gathered_scale, out_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi,
-                           gather_dtype=gd)
-
-    def _plain_layout(self, transposed: bool, F: int, gathered_scale):
+    def _plain_layout(self, D: _Direction, F: int, gathered_scale):
         """``(name, layout)`` of the plain float32 XCD-local product of width ``F``; ``name`` keys this view's per-layout
         values, id words and compacted copies.
 
@@ -929,41 +922,82 @@ class CSRGraph:
         the 8-slice layout; the bf16 gather stays on that layout too (there the library runs its owned form for the
         measured bf16 classes), as does every shape the library answers 8 for.  Which layout a
         product runs on depends on the product alone, never on what the graph has built before (:meth:`_layout_of`)."""
-        S = self._S
-        n_rows, n_cols = (S.n_src, S.n_dst) if transposed else (S.n_dst, S.n_src)
         n = SlicedCSR.N_SLICES
         mf = self._mult_form()
         if (self._coo_vals is None or mf is not None) and (self._keep is None or COMPACT_DROPPED):
-            n = _lib.sliced_layout_slices(n_rows, n_cols, F, mf is not None)
-            scaled = gathered_scale is not None or (mf is not None and (mf[0] == "row") == transposed)
-            if n != SlicedCSR.N_SLICES and scaled and not SlicedCSR._prescale_rule(n_cols * F * 4, False, n_rows, n, self.nnz):
+            n = _lib.sliced_layout_slices(D.n_rows, D.n_cols, F, mf is not None)
+            scaled = gathered_scale is not None or (mf is not None and (mf[0] == "row") == D.transposed)
+            if n != SlicedCSR.N_SLICES and scaled and not SlicedCSR._prescale_rule(D.n_cols * F * 4, False, D.n_rows, n, self.nnz):
                 n = SlicedCSR.N_SLICES  # the scale would be gathered inside the kernel: the pair's product
-        return self._layout_of(transposed, n)
+        return self._layout_of(D, n)
 
-    def _layout_of(self, transposed: bool, n_slices: int = SlicedCSR.N_SLICES):
-        """``(name, layout)``: the XCD-sliced layout of ``n_slices`` source slices, built on first use.  The first layout
-        a graph builds per direction sits in ``sliced`` / ``sliced_t`` (name ``"sliced"`` / ``"sliced_t"``), one of
-        another slice count beside it in ``wide`` (name ``"sliced/<n>"``): a graph whose products all run on one
-        layout holds one."""
-        S = self._S
-        base = "sliced_t" if transposed else "sliced"
-        first = S.sliced_t if transposed else S.sliced
+    def _layout_of(self, D, n_slices: int = SlicedCSR.N_SLICES):
+        """``(name, layout)``: the XCD-sliced layout of ``n_slices`` source slices of direction ``D`` (the record, or
+        whether it is the transposed one), built on first use.  The first layout a graph builds per direction sits in
+        the record (``sliced`` / ``sliced_t``, name ``"sliced"`` / ``"sliced_t"``), one of another slice count beside
+        it in ``wide`` (name ``"sliced/<n>"``): a graph whose products all run on one layout holds one."""
+        if D.__class__ is not _Direction:
+            D = self._S.bwd if D else self._S.fwd
+        first = D.sliced
         if first is not None and first.n_slices == n_slices:
-            return base, first
-        layout = None if first is None else S.wide.get((transposed, n_slices))
+            return D.sliced_key, first
+        layout = None if first is None else self._S.wide.get((D.transposed, n_slices))
         if layout is None:
-            if transposed:
-                indptr_t, indices_t, eid_t, _ = self._t_struct()
-                layout = SlicedCSR.from_csr(indptr_t, indices_t, eid_t, S.n_src, S.n_dst, n_slices)
-            else:
-                layout = SlicedCSR.from_csr(S.indptr, S.indices, S.eid, S.n_dst, S.n_src, n_slices)  # one partition pass, no sort
+            self._built(D)
+            layout = SlicedCSR.from_csr(D.indptr, D.indices, D.eid, D.n_rows, D.n_cols, n_slices)  # one partition pass, no sort
             if first is not None:
-                S.wide[(transposed, n_slices)] = layout
-            elif transposed:
-                S.sliced_t = layout
+                self._S.wide[(D.transposed, n_slices)] = layout
             else:
-                S.sliced = layout
-        return (base if first is None else "%s/%d" % (base, n_slices)), layout
+                D.sliced = layout
+        return (D.sliced_key if first is None else "%s/%d" % (D.sliced_key, n_slices)), layout
+
+    def _product(self, D: _Direction, X, gathered_scale, out_scale, out, epi, gather_dtype):
+        """``diag(out_scale) M diag(gathered_scale) X`` with ``M`` the matrix of direction ``D`` (``A`` or ``A^T``): every
+        route decision of :meth:`spmm` and :meth:`spmm_t`.  ``gathered_scale`` multiplies the gathered rows (with a bf16
+        gather it is folded into the conversion of a float32 ``X``), ``out_scale`` the output rows."""
+        if D.regular is None:  # one-time readback of this direction's maximum degree, when it can matter
+            self._decide_regular(X, D)
+        two_d = X.dim() == 2
+        F = X.shape[1] if two_d else 0
+        bf16 = self._bf16_request(X, out, gather_dtype, D)  # True: the plain XCD-local form, checked for this X and out
+        long_rows = not bf16 and two_d and bool(D.regular) and self._few_long_rows(F, D.n_rows, D.n_cols)
+        if bf16 or (two_d and not long_rows and self._use_sliced(F, D.n_rows, D.n_cols, D.regular) and _sliced_ok(X, out)):
+            # the bf16 gather stays on the pair's 8 slices: the library runs its owned form on them where it wins (DESIGN §4.12)
+            name, layout = self._layout_of(D) if bf16 else self._plain_layout(D, F, gathered_scale)
+            mult = self._mult_ids(name, layout)
+            if mult is not None:
+                # values = scale x multiplicity.  The scale is indexed by the destination ("row": D^-1 M) or by the source
+                # ("col": M D^-1): the output rows of one direction, the gathered rows of the other
+                if (mult[0] == "row") != D.transposed:
+                    out_scale = self._fold(mult[1], out_scale)
+                else:
+                    gathered_scale = self._fold(mult[1], gathered_scale)
+            gd = None
+            if bf16:
+                if X.dtype != torch.bfloat16:
+                    gd = torch.bfloat16
+                elif gathered_scale is not None:
+                    raise RuntimeError("a bfloat16 X cannot take a scale on the gathered rows (src_scale, or the row scale of this "
+                                       "graph's `scale x multiplicity` values): it is applied in float32 before the one rounding — "
+                                       "pass the float32 table")
+            c = self._compacted(name, layout, mult)
+            if c is not None:
+                return c.spmm(X, gathered_scale, out_scale, out, epi=epi, gather_dtype=gd)
+            if mult is not None:
+                return layout.spmm(X, gathered_scale, out_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2],
+                                   id_mult=True, gather_dtype=gd)
+            return layout.spmm(X, gathered_scale, out_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi,
+                               gather_dtype=gd)
+        if two_d and _sliced_ok(X, out) and (self._use_split(F, D.n_rows, D.n_cols, D.regular) or (
+                long_rows and self._use_sliced(F, D.n_rows, D.n_cols, D.regular))):
+            split = D.split
+            if split is None:
+                split = D.split = _SplitSliced(D.indptr, D.eid, D.cols_coo, D.n_rows, D.n_cols)
+            c = self._compacted(D.split_key, split.sliced)
+            return split.spmm(X, _prep_scale(gathered_scale, D.n_cols, D.gathered_name), _prep_scale(out_scale, D.n_rows, D.out_name),
+                              out, None if c is not None else self._vals_for(D.split_key, split.sliced.eid), keep=self._keep,
+                              epi=epi, compacted=c, c_vals=self._combine_vals(D.split_key, split))
+        return self._run(D, X, gathered_scale, out_scale, out, epi)
 
     def spmm(self, X, src_scale=None, dst_scale=None, out=None, epi=None, gather_dtype=None):
         """``diag(dst_scale) A diag(src_scale) X`` (no autograd).  Picks the XCD-local sliced kernel when the
@@ -971,73 +1005,12 @@ class CSRGraph:
         (act, slope, out_mask, mask_scale), fused into the kernel that writes the result.  ``gather_dtype`` (default:
         :func:`gather_precision`'s): ``torch.bfloat16`` gathers from a bf16 copy of ``diag(src_scale) X`` where
         :meth:`takes_bf16_gather` holds, and is the float32 product elsewhere."""
-        S = self._S
-        if S.regular is None:
-            self._decide_regular(X, False)
-        if self._bf16_request(X, out, gather_dtype, False):
-            return self._spmm_bf16(X, src_scale, dst_scale, out, epi, False)
-        long_rows = X.dim() == 2 and bool(S.regular) and self._few_long_rows(X.shape[1], S.n_dst, S.n_src)
-        if (X.dim() == 2 and not long_rows and self._use_sliced(X.shape[1], S.n_dst, S.n_src, S.regular)
-                and _sliced_ok(X, out)):
-            name, layout = self._plain_layout(False, X.shape[1], src_scale)
-            mult = self._mult_ids(name, layout)
-            if mult is not None:  # values = scale x multiplicity: a destination (D^-1 M) or a source (M D^-1) scale
-                if mult[0] == "row":
-                    dst_scale = self._fold(mult[1], dst_scale)
-                else:
-                    src_scale = self._fold(mult[1], src_scale)
-            c = self._compacted(name, layout, mult)
-            if c is not None:
-                return c.spmm(X, src_scale, dst_scale, out, epi=epi)
-            if mult is not None:
-                return layout.spmm(X, src_scale, dst_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2], id_mult=True)
-            return layout.spmm(X, src_scale, dst_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep, epi=epi)
-        if X.dim() == 2 and _sliced_ok(X, out) and (self._use_split(X.shape[1], S.n_dst, S.n_src, S.regular) or (
-                long_rows and self._use_sliced(X.shape[1], S.n_dst, S.n_src, S.regular))):
-            if S.split is None:
-                S.split = _SplitSliced(S.indptr, S.eid, S.src, S.n_dst, S.n_src)
-            c = self._compacted("split", S.split.sliced)
-            return S.split.spmm(X, _prep_scale(src_scale, S.n_src, "src_scale"), _prep_scale(dst_scale, S.n_dst, "dst_scale"),
-                                out, None if c is not None else self._vals_for("split", S.split.sliced.eid), keep=self._keep,
-                                epi=epi, compacted=c, c_vals=self._combine_vals("split", S.split))
-        return self._run(S.indptr, S.indices, self.vals, self._plan_if_needed(S.plan, S.max_deg), S.n_dst, S.n_src, X,
-                         src_scale, dst_scale, out, S.eid, epi)
+        return self._product(self._S.fwd, X, src_scale, dst_scale, out, epi, gather_dtype)
 
     def spmm_t(self, dY, src_scale=None, dst_scale=None, out=None, gather_dtype=None):
         """``diag(src_scale) A^T diag(dst_scale) dY`` — the backward of :meth:`spmm`.  With a bf16 gather ``dst_scale``
         is folded into the conversion of ``dY`` and ``src_scale`` is applied by the plane reduce."""
-        S = self._S
-        indptr_t, indices_t, eid_t, plan_t = self._t_struct()
-        if S.regular_t is None:  # one-time readback of the reversed graph's maximum degree, when it can matter
-            self._decide_regular(dY, True)
-        if self._bf16_request(dY, out, gather_dtype, True):
-            return self._spmm_bf16(dY, dst_scale, src_scale, out, None, True)
-        long_rows = dY.dim() == 2 and bool(S.regular_t) and self._few_long_rows(dY.shape[1], S.n_src, S.n_dst)
-        if (dY.dim() == 2 and not long_rows and self._use_sliced(dY.shape[1], S.n_src, S.n_dst, S.regular_t)
-                and _sliced_ok(dY, out)):
-            name, layout = self._plain_layout(True, dY.shape[1], dst_scale)
-            mult = self._mult_ids(name, layout)
-            if mult is not None:  # (D^-1 M)^T = M^T D^-1: the scale multiplies the gathered (destination-node) rows; (M D^-1)^T: the output rows
-                if mult[0] == "row":
-                    dst_scale = self._fold(mult[1], dst_scale)
-                else:
-                    src_scale = self._fold(mult[1], src_scale)
-            c = self._compacted(name, layout, mult)
-            if c is not None:
-                return c.spmm(dY, dst_scale, src_scale, out)
-            if mult is not None:
-                return layout.spmm(dY, dst_scale, src_scale, out, vals=None, keep=self._keep, indices=mult[2], id_mult=True)
-            return layout.spmm(dY, dst_scale, src_scale, out, vals=self._vals_for(name, layout.eid), keep=self._keep)
-        if dY.dim() == 2 and _sliced_ok(dY, out) and (self._use_split(dY.shape[1], S.n_src, S.n_dst, S.regular_t) or (
-                long_rows and self._use_sliced(dY.shape[1], S.n_src, S.n_dst, S.regular_t))):
-            if S.split_t is None:
-                S.split_t = _SplitSliced(indptr_t, eid_t, S.dst, S.n_src, S.n_dst)
-            c = self._compacted("split_t", S.split_t.sliced)
-            return S.split_t.spmm(dY, _prep_scale(dst_scale, S.n_dst, "dst_scale"), _prep_scale(src_scale, S.n_src, "src_scale"),
-                                  out, None if c is not None else self._vals_for("split_t", S.split_t.sliced.eid), keep=self._keep,
-                                  compacted=c, c_vals=self._combine_vals("split_t", S.split_t))
-        return self._run(indptr_t, indices_t, self._vals_for("csr_t", eid_t), self._plan_if_needed(plan_t, S.max_deg_t), S.n_src, S.n_dst, dY,
-                         dst_scale, src_scale, out, eid_t)
+        return self._product(self._built(self._S.bwd), dY, dst_scale, src_scale, out, None, gather_dtype)
 
 
 class _SpMM(torch.autograd.Function):
