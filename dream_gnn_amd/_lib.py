@@ -132,6 +132,16 @@ LAYOUT_SIGNATURES = {
     "dgmi_sliced_layout_slices": (ctypes.c_int32, [_i64, _i64, _i64, ctypes.c_int32]),
 }
 
+# name -> (restype, argtypes); mirrors include/dgmi_train.h (its own table, for the same reason).
+_TRAIN_OPERANDS = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                   ctypes.c_float, _vp]
+TRAIN_SIGNATURES = {
+    "dgmi_pair_mlp_train_workspace_bytes": (ctypes.c_size_t, [_i64]),
+    "dgmi_pair_mlp_train_forward_f32": (ctypes.c_int, _TRAIN_OPERANDS + [_vp, _vp, _vp]),
+    "dgmi_pair_mlp_train_backward_f32": (ctypes.c_int, _TRAIN_OPERANDS + [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                                          ctypes.c_size_t, _vp]),
+}
+
 
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
@@ -146,8 +156,8 @@ def _load() -> ctypes.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
                               + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
                               + list(GIVEN_SIGNATURES.items()) + list(CURVE_SIGNATURES.items())
-                              + list(LAYOUT_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the eight headers declare
+                              + list(LAYOUT_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the nine headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

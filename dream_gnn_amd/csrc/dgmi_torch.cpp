@@ -31,6 +31,7 @@
 #include "dgmi_given.h"
 #include "dgmi_pairs.h"
 #include "dgmi_rank.h"
+#include "dgmi_train.h"
 
 namespace {
 
@@ -82,7 +83,7 @@ Tensor scratch(const Tensor& like, size_t nbytes, int kind) {
   }
   return it->second;
 }
-enum { kPartials = 0, kPlanes = 1, kBuilder = 2, kPairs = 3 };
+enum { kPartials = 0, kPlanes = 1, kBuilder = 2, kPairs = 3, kTrain = 4 };
 
 struct Keep {
   const int32_t* eid = nullptr;
@@ -649,6 +650,86 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> pair_mlp_rank_list(const Tensor& X, c
   return {o.logit, o.above, o.total, o.info};
 }
 
+// the decoder MLP on the TRAINING pair list (dgmi_pairs_train.hip): logits with dropout keyed by `seed` (one int64 on the
+// device, read by the kernels), and every gradient from a recompute.  int32 ids as EdgePairs keeps them; info[0] = a
+// listed id is out of range.  The backward's workspace (dZ2 and the workgroups' partial sums) is the per-(device, stream)
+// scratch; nothing here synchronises, so both ops can be captured.
+struct TrainOperands {
+  Dense x, c;
+  Tensor W2, b2, w3, b3, pq, pc, seed;
+  int64_t n_pairs;
+  float p;
+};
+
+TrainOperands train_operands(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2, const Tensor& w3,
+                             const Tensor& b3, const Tensor& pair_query, const Tensor& pair_cand, double p, const Tensor& seed) {
+  TrainOperands o;
+  o.x = dense16_of(X, "X");
+  o.c = dense16_of(C, "C");
+  TORCH_CHECK(o.x.F == 128 && o.c.F == 128, "X and C must have 128 columns (the decoder's lin1 width), got ", o.x.F, " and ", o.c.F);
+  TORCH_CHECK(C.device() == X.device(), "tensors on different devices: C on ", C.device().str(), " vs ", X.device().str());
+  check(W2, at::kFloat, 2, "W2", X);
+  TORCH_CHECK(W2.size(0) == 64 && W2.size(1) == 128, "W2 must be (64, 128), got (", W2.size(0), ", ", W2.size(1), ")");
+  check(b2, at::kFloat, 1, "b2", X);
+  check(w3, at::kFloat, 1, "w3", X);
+  check(b3, at::kFloat, 1, "b3", X);
+  TORCH_CHECK(b2.numel() == 64 && w3.numel() == 64 && b3.numel() == 1, "b2 / w3 / b3 must have 64 / 64 / 1 entries");
+  check(pair_query, at::kInt, 1, "pair_query", X);
+  check(pair_cand, at::kInt, 1, "pair_cand", X);
+  TORCH_CHECK(pair_query.numel() == pair_cand.numel(), "pair_query / pair_cand length mismatch");
+  TORCH_CHECK(pair_query.numel() <= (int64_t)INT32_MAX, "at most 2^31 - 1 listed pairs");
+  check(seed, at::kLong, 1, "seed", X);
+  TORCH_CHECK(seed.numel() == 1, "seed must hold ONE int64, got ", seed.numel());
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout p must be in [0, 1), got ", p);
+  o.W2 = contiguous16(W2), o.b2 = b2, o.w3 = w3, o.b3 = b3, o.pq = pair_query, o.pc = pair_cand, o.seed = seed;
+  o.n_pairs = pair_query.numel();
+  o.p = (float)p;
+  return o;
+}
+
+std::tuple<Tensor, Tensor> pair_mlp_train_forward(const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2,
+                                                  const Tensor& w3, const Tensor& b3, const Tensor& pair_query,
+                                                  const Tensor& pair_cand, double p, const Tensor& seed) {
+  TrainOperands o = train_operands(X, C, W2, b2, w3, b3, pair_query, pair_cand, p, seed);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(o.x.t.device());
+  auto opts = o.x.t.options();
+  Tensor logit = at::empty({o.n_pairs}, opts.dtype(at::kFloat));
+  Tensor info = at::zeros({2}, opts.dtype(at::kInt));
+  if (o.n_pairs == 0) return {logit, info};
+  check_status(dgmi_pair_mlp_train_forward_f32(o.x.t.data_ptr<float>(), o.x.ld, o.x.rows, o.c.t.data_ptr<float>(), o.c.ld, o.c.rows,
+                                               128, 64, o.W2.data_ptr<float>(), o.b2.data_ptr<float>(), o.w3.data_ptr<float>(),
+                                               o.b3.data_ptr<float>(), o.pq.data_ptr<int32_t>(), o.pc.data_ptr<int32_t>(),
+                                               o.n_pairs, o.p, o.seed.data_ptr<int64_t>(), logit.data_ptr<float>(),
+                                               info.data_ptr<int32_t>(), stream_of(o.x.t)),
+               "dgmi_pair_mlp_train_forward_f32");
+  return {logit, info};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> pair_mlp_train_backward(
+    const Tensor& X, const Tensor& C, const Tensor& W2, const Tensor& b2, const Tensor& w3, const Tensor& b3,
+    const Tensor& pair_query, const Tensor& pair_cand, double p, const Tensor& seed, const Tensor& dlogit) {
+  TrainOperands o = train_operands(X, C, W2, b2, w3, b3, pair_query, pair_cand, p, seed);
+  check(dlogit, at::kFloat, 1, "dlogit", X);
+  TORCH_CHECK(dlogit.numel() == o.n_pairs, "dlogit has ", dlogit.numel(), " entries, the list has ", o.n_pairs, " pairs");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(o.x.t.device());
+  auto opts = o.x.t.options().dtype(at::kFloat);
+  Tensor dz1 = at::empty({o.n_pairs, 128}, opts);
+  Tensor info = at::zeros({2}, opts.dtype(at::kInt));
+  if (o.n_pairs == 0) return {dz1, at::zeros({64, 128}, opts), at::zeros({64}, opts), at::zeros({64}, opts), at::zeros({1}, opts), info};
+  Tensor dW2 = at::empty({64, 128}, opts), db2 = at::empty({64}, opts), dw3 = at::empty({64}, opts), db3 = at::empty({1}, opts);
+  const size_t wbytes = dgmi_pair_mlp_train_workspace_bytes(o.n_pairs);
+  Tensor ws = scratch(o.x.t, wbytes < 256 ? 256 : wbytes, kTrain);
+  check_status(dgmi_pair_mlp_train_backward_f32(o.x.t.data_ptr<float>(), o.x.ld, o.x.rows, o.c.t.data_ptr<float>(), o.c.ld, o.c.rows,
+                                                128, 64, o.W2.data_ptr<float>(), o.b2.data_ptr<float>(), o.w3.data_ptr<float>(),
+                                                o.b3.data_ptr<float>(), o.pq.data_ptr<int32_t>(), o.pc.data_ptr<int32_t>(),
+                                                o.n_pairs, o.p, o.seed.data_ptr<int64_t>(), dlogit.data_ptr<float>(),
+                                                dz1.data_ptr<float>(), 128, dW2.data_ptr<float>(), db2.data_ptr<float>(),
+                                                dw3.data_ptr<float>(), db3.data_ptr<float>(), info.data_ptr<int32_t>(),
+                                                ws.data_ptr(), (size_t)ws.numel(), stream_of(o.x.t)),
+               "dgmi_pair_mlp_train_backward_f32");
+  return {dz1, dW2, db2, dw3, db3, info};
+}
+
 // exact AUROC / AUPR of scored samples, overall (n_segments = 0) or per segment (dgmi_curve.hip): count = (S, 6) int64
 // rows (P, N, TP at the threshold, FP at the threshold, groups, U2), area = (S, 2) float64 rows (auroc, aupr), info =
 // [flag word] (bit 0 NaN score, bit 1 label not 0 / 1, bit 2 segment id out of range).  Any shape of score (flattened);
@@ -1109,6 +1190,18 @@ TORCH_LIBRARY_IMPL(dreamgnn_mi, Autograd, m) { m.impl("spmm_csr", spmm_csr_autog
 // The evaluation metrics, registered as a fragment of their own: curve_areas reads scores and writes statistics, it
 // is no operand of a product, so its operand forms are tested with its arithmetic (tests/test_gpu_curve.py) and not in
 // the binding case table, which holds one case per op of the block above (tests/_binding_cases.py).
+TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, train) {
+  train.def("pair_mlp_train_forward(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor pair_query, "
+            "Tensor pair_cand, float p, Tensor seed) -> (Tensor, Tensor)");
+  train.def("pair_mlp_train_backward(Tensor X, Tensor C, Tensor W2, Tensor b2, Tensor w3, Tensor b3, Tensor pair_query, "
+            "Tensor pair_cand, float p, Tensor seed, Tensor dlogit) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, train) {
+  train.impl("pair_mlp_train_forward", pair_mlp_train_forward);
+  train.impl("pair_mlp_train_backward", pair_mlp_train_backward);
+}
+
 TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, metrics) {
   metrics.def("curve_areas(Tensor score, Tensor label, Tensor? segment, int n_segments, float threshold) -> (Tensor count, Tensor area, Tensor info)");
 }

@@ -150,8 +150,10 @@ def _edge_linear(lin: nn.Linear, x):
 class MLPDecoder(nn.Module):
     """Per-edge gather-concat then 2F->128->64->1 MLP — layers.py:341-375."""
 
-    def __init__(self, in_units, dropout_rate=0.1):
+    def __init__(self, in_units, dropout_rate=0.1, fused_training=False):
         super().__init__()
+        if fused_training:
+            self.fused_training = True
         self.dropout = nn.Dropout(dropout_rate)
         self.sigmoid = nn.Sigmoid()
         self.lin1 = nn.Linear(2 * in_units, 128)
@@ -170,8 +172,21 @@ class MLPDecoder(nn.Module):
     #: reference's literal order (gather-concat, then lin1 over edges).
     fuse_lin1 = True
 
+    #: Opt-in: the whole MLP over the pair list as ONE HIP kernel forward and a recompute backward
+    #: (``ops.pair_mlp_train``) on the split ``lin1`` tables.  No E x 128 / E x 64 tensor is kept for the backward.  The
+    #: dropout masks come from a hash keyed by a device-drawn seed, NOT from torch's RNG stream (one ``randint`` draw per
+    #: forward instead of two mask draws), which is why the default stays the torch chain.  fp32 HIP inputs only.
+    fused_training = False
+
     def forward(self, graph, drug_feat, dis_feat):
         pairs = graph.edge_pairs()
+        if (self.fused_training and drug_feat.is_cuda and dis_feat.is_cuda and drug_feat.dtype == torch.float32
+                and dis_feat.dtype == torch.float32):
+            P, Q = self._split_lin1(drug_feat, dis_feat)
+            if self.training or torch.is_grad_enabled():
+                p = float(self.dropout.p) if self.training else 0.0
+                return ops.pair_mlp_train(P, Q, *self._tail(), pairs, p).unsqueeze(-1)
+            return ops.pair_mlp_score_list(P, Q, *self._tail(), pairs.src, pairs.dst).unsqueeze(-1)
         if self.fuse_lin1:
             Fd = drug_feat.shape[1]
             w = self.lin1.weight

@@ -1423,6 +1423,69 @@ def pair_mlp_score_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: 
     return logit
 
 
+class _PairMlpTrain(torch.autograd.Function):
+    """The decoder MLP on the training pair list, fused (``dgmi_pairs_train.hip``).  Forward: one kernel, saves the
+    operands (node tables, parameters, the seed) and nothing per pair.  Backward: the kernels recompute the hidden layers
+    with the same masks and return ``dZ1`` (E x 128) and the parameter gradients; ``dP`` / ``dQ`` are the two segment
+    sums of :class:`_GatherAdd`."""
+
+    @staticmethod
+    def forward(ctx, P, Q, W2, b2, w3, b3, pairs: EdgePairs, p: float, seed):
+        _check_tables(P, Q, pairs.n_src, pairs.n_dst)
+        logit, _ = _T.pair_mlp_train_forward(P, Q, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1), pairs.src, pairs.dst,
+                                             p, seed)
+        ctx.pairs, ctx.p = pairs, p
+        ctx.save_for_backward(P, Q, W2, b2, w3, b3, seed)
+        return logit
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogit):
+        P, Q, W2, b2, w3, b3, seed = ctx.saved_tensors
+        pairs = ctx.pairs
+        dZ1, dW2, db2, dw3, db3, _ = _T.pair_mlp_train_backward(P, Q, W2, b2.reshape(-1), w3.reshape(-1), b3.reshape(-1),
+                                                                pairs.src, pairs.dst, ctx.p, seed, dlogit.contiguous())
+        need = ctx.needs_input_grad
+        if pairs.E == 0:  # nothing to sum: no segment layout of an empty list is built
+            dP, dQ = (torch.zeros_like(P) if need[0] else None), (torch.zeros_like(Q) if need[1] else None)
+        else:
+            dP = pairs.by_src().spmm(dZ1) if need[0] else None
+            dQ = pairs.by_dst().spmm(dZ1) if need[1] else None
+        return (dP, dQ, dW2 if need[2] else None, db2.reshape(b2.shape) if need[3] else None,
+                dw3.reshape(w3.shape) if need[4] else None, db3.reshape(b3.shape) if need[5] else None, None, None, None)
+
+
+def pair_mlp_train(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor,
+                   pairs: EdgePairs, p: float, seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``logit[e] = b3 + w3 . m2 relu(W2 (m1 relu(P[src_e] + Q[dst_e])) + b2)`` over the decoder's pair list, in training:
+    ``m1`` / ``m2`` are dropout factors (``1 / (1 - p)`` or 0) drawn by a hash of ``(seed, layer, e, unit)``
+    (``csrc/dgmi_pair_dropout.h``) — NOT torch's RNG stream.  One HIP kernel forward; the backward recomputes the hidden
+    layers, so autograd keeps no ``E x H`` tensor.  Differentiable once in ``P``, ``Q`` and the four parameters; all sums
+    are free of float atomics (bit-identical from run to run for one seed).  With ``p = 0`` every logit is
+    :func:`pair_mlp_score_list`'s, bit for bit.
+
+    ``seed``: a 1-element int64 device tensor, used as is (the kernels read it from device memory, so a captured step
+    follows whatever the tensor holds at replay); ``None`` draws one on the device from torch's graph-aware generator.
+    The tensor used is kept in ``pair_mlp_train.last_seed``.  The ids were range-checked by :class:`EdgePairs`; nothing
+    here synchronises."""
+    if not isinstance(pairs, EdgePairs):
+        raise TypeError("pairs must be an ops.EdgePairs, got %s" % type(pairs).__name__)
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout p must be in [0, 1), got %r" % (p,))
+    _require_device(P, Q, W2, b2, w3, b3, seed)
+    if seed is None:
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=P.device)
+    elif seed.dtype != torch.int64 or seed.numel() != 1:
+        raise ValueError("seed must be a 1-element int64 device tensor")
+    seed = seed.reshape(1)
+    pair_mlp_train.last_seed = seed
+    return _PairMlpTrain.apply(P, Q, W2, b2, w3, b3, pairs, p, seed)
+
+
+pair_mlp_train.last_seed = None
+
+
 def pair_mlp_rank_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
                        b3: torch.Tensor, pair_query: torch.Tensor, pair_cand: torch.Tensor,
                        known_query: Optional[torch.Tensor] = None,
