@@ -67,7 +67,9 @@ struct PairDropout {
 inline PairDropout pair_dropout_of(float p) {
   PairDropout d;
   const double q = 1.0 - (double)p;
-  const uint64_t t = (uint64_t)(q * 4294967296.0);  // 2^32 at p = 0 (and for a p below 2^-33): nothing is dropped
+  // 2^32 at p = 0 (and for p <= 2^-54, where 1 - p is 1.0 in double): nothing is dropped.  A larger p below 2^-32
+  // gives 2^32 - 1: only a unit whose hash is 0xffffffff is dropped.
+  const uint64_t t = (uint64_t)(q * 4294967296.0);
   d.all = t > 0xffffffffull ? 1u : 0u;
   d.thr = d.all ? 0xffffffffu : (uint32_t)t;
   d.scale = (float)(1.0 / q);

@@ -28,6 +28,15 @@ extern "C" {
  * the kernels, so a captured launch draws a new mask whenever the caller has written a new seed before a replay.  With
  * p = 0 every logit is bit-identical to dgmi_pair_mlp_score_list_f32's for the same operands.
  *
+ * Non-finite operands.  A DROPPED unit is exactly 0, whatever value lies under it: the factor 0 is a select, not a
+ * product, so a NaN or an Inf in X or C does not pass a dropped unit, forward or backward.  A KEPT unit follows IEEE:
+ * relu keeps NaN (relu(NaN) = NaN, relu(+Inf) = +Inf, relu(-Inf) = 0), 0 * Inf and Inf - Inf are NaN, and the sums
+ * carry them on.  The relu gate of the backward is [z > 0], which is false for NaN.  A pair whose every non-finite unit
+ * is dropped therefore has a finite logit and finite dz1; one pair's values never reach another pair's logit or dz1
+ * row.  out_dW2 and out_dw3 are sums over the pairs and follow IEEE too: a kept non-finite h1[e, k] (h2[e, h]) makes
+ * column k of out_dW2 (entry h of out_dw3) NaN even where dlogit[e] = 0, because 0 * NaN is NaN.  This is NOT the torch
+ * chain, whose dropout multiplies by a mask (NaN * 0 = NaN under a dropped unit as well).
+ *
  * dgmi_pair_mlp_train_forward_f32: out_logit[e], e < n_pairs.  A listed pair with an id outside
  * [0, n_query) x [0, n_cand) reads nothing, sets out_info[0] = 1 and gets logit NaN; out_info is 2 int32, cleared first.
  *

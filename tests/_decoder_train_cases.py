@@ -69,28 +69,47 @@ def masks(seed, E, p):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the float64 restatement
-def reference(P, Q, W2, b2, w3, b3, src, dst, p, seed, g, absolute=False):
+def reference(P, Q, W2, b2, w3, b3, src, dst, p, seed, g, absolute=False, form="product", open_gates=False):
     """Logits and every gradient in float64 with the restated masks.  ``absolute=True``: the same expressions on the
-    absolute values of every operand, with the gates (masks, relu) of the true computation: sum|terms|."""
+    absolute values of every operand, with the gates (masks, relu) of the true computation: sum|terms|.
+
+    ``form``: how a gate meets a value.  ``"product"`` multiplies by the 0 / scale factor, as the torch chain does;
+    ``"select"`` is the kernels' contract (include/dgmi_train.h): a unit whose gate is closed is exactly 0 whatever lies
+    under it, an open one is ``value * scale`` under IEEE rules (relu keeps NaN, ``relu(+Inf) = +Inf``, the backward's
+    relu gate ``[z > 0]`` is false for NaN).  On finite operands the two forms are the same bits.
+
+    ``open_gates=True`` (with ``absolute``): every mask and relu gate open, which bounds sum|terms| under ANY seed."""
+    if form not in ("product", "select"):
+        raise ValueError(form)
     P, Q, W2, b2, w3, g = (np.asarray(a, dtype=np.float64) for a in (P, Q, W2, b2, w3, g))
     b3 = float(np.asarray(b3, dtype=np.float64).reshape(-1)[0])
     w3 = w3.reshape(-1)
     E = len(src)
     m1, m2 = masks(seed, E, p)
     s = float(scale(p))
-    z1 = P[src] + Q[dst]
-    h1 = np.maximum(z1, 0.0) * m1 * s
-    z2 = h1 @ W2.T + b2
-    gate1, gate2 = m1 * s * (z1 > 0), m2 * s * (z2 > 0)
-    if absolute:
-        P, Q, W2, b2, w3, g, b3 = np.abs(P), np.abs(Q), np.abs(W2), np.abs(b2), np.abs(w3), np.abs(g), abs(b3)
-        h1 = (P[src] + Q[dst]) * gate1
+    if form == "select":
+        gated = lambda x, gate: np.where(gate, x * s, 0.0)  # noqa: E731
+    else:
+        gated = lambda x, gate: x * (gate * s)  # noqa: E731
+    with np.errstate(invalid="ignore"):  # Inf - Inf and 0 * Inf are NaN on purpose
+        z1 = P[src] + Q[dst]
+        h1 = gated(np.maximum(z1, 0.0), m1)
         z2 = h1 @ W2.T + b2
-    h2 = z2 * gate2 if absolute else np.maximum(z2, 0.0) * m2 * s
-    out = {"logit": h2 @ w3 + b3, "z2": z2}
-    dz2 = g[:, None] * w3[None, :] * gate2
-    dz1 = (dz2 @ W2) * gate1
-    out["dW2"], out["db2"], out["dw3"], out["db3"] = dz2.T @ h1, dz2.sum(0), (g[:, None] * h2).sum(0), np.array([g.sum()])
+        gate1, gate2 = m1 & (z1 > 0), m2 & (z2 > 0)
+        if open_gates:
+            if not absolute:
+                raise ValueError("open_gates bounds the absolute form only")
+            gate1, gate2, m1, m2 = (np.ones_like(x) for x in (gate1, gate2, m1, m2))
+        if absolute:
+            P, Q, W2, b2, w3, g, b3 = np.abs(P), np.abs(Q), np.abs(W2), np.abs(b2), np.abs(w3), np.abs(g), abs(b3)
+            h1 = gated(P[src] + Q[dst], gate1)
+            z2 = h1 @ W2.T + b2
+        h2 = gated(z2, gate2) if absolute else gated(np.maximum(z2, 0.0), m2)
+        out = {"logit": h2 @ w3 + b3, "z2": z2}
+        dz2 = gated(g[:, None] * w3[None, :], gate2)
+        dz1 = gated(dz2 @ W2, gate1)
+        out["dW2"], out["db2"], out["dw3"], out["db3"] = dz2.T @ h1, dz2.sum(0), (g[:, None] * h2).sum(0), np.array([g.sum()])
+    out["dz1"] = dz1
     out["dP"], out["dQ"] = np.zeros_like(P), np.zeros_like(Q)
     np.add.at(out["dP"], src, dz1)
     np.add.at(out["dQ"], dst, dz1)
@@ -98,6 +117,13 @@ def reference(P, Q, W2, b2, w3, b3, src, dst, p, seed, g, absolute=False):
 
 
 GRADS = ("dP", "dQ", "dW2", "db2", "dw3", "db3")
+MODULE_GRADS = ("dhd", "dhs", "dW1", "db1")
+
+
+def ref_of(d, p, seed, g=None, **kw):
+    """``reference`` on a design's operands (``g``: another upstream gradient than the design's)."""
+    return reference(d["P"], d["Q"], d["W2"], d["b2"], d["w3"], d["b3"], d["src"], d["dst"], p, seed,
+                     d["g"] if g is None else g, **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -136,10 +162,109 @@ def exact_design(E, seed=0):
     return dict(P=P, Q=Q, W2=W2, b2=b2, w3=w3, b3=b3, src=src, dst=dst, g=g, n_src=n_src, n_dst=n_dst)
 
 
-def exact_margin(d, p, seed):
-    """The largest sum of absolute terms over all outputs of a design: below 2^24 means exact in fp32, in any order."""
-    a = reference(d["P"], d["Q"], d["W2"], d["b2"], d["w3"], d["b3"], d["src"], d["dst"], p, seed, d["g"], absolute=True)
+def exact_margin(d, p, seed, g=None):
+    """The largest sum of absolute terms over all outputs of a design: below 2^24 means exact in fp32, in any order.
+    A module design (``module_design``) adds the two ``lin1`` tables and the four gradients behind them.  ``seed=None``:
+    with every gate open, a bound for any seed."""
+    kw = dict(absolute=True, open_gates=seed is None)
+    seed = 0 if seed is None else seed
+    if "hd" in d:
+        a = module_reference(d, p, seed, g=g, **kw)
+        return max(float(np.max(a[k])) for k in ("P", "Q", "logit", "z2") + GRADS + MODULE_GRADS)
+    a = ref_of(d, p, seed, g, **kw)
     return max(float(np.max(a[k])) for k in ("logit", "z2") + GRADS)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the module route: P = hd Wa^T + b1, Q = hs Wb^T in front of the fused op
+MODULE_F = 8
+
+
+def module_design(E, seed=0):
+    """Integer embeddings ``hd`` (37 x 8), ``hs`` (29 x 8) in [-2, 2], ``lin1.weight`` (128 x 16) in [-1, 1] with
+    density 0.4, ``lin1.bias`` in [-1, 1]; ``lin2`` / ``lin3``, the pair list and the upstream gradient as in
+    ``exact_design``.  Every operand is a bf16 number, so a GEMM library may round its inputs to bf16 / TF32 and still
+    be exact as long as it accumulates in fp32 (the GPU test asserts that on these very operands).  ``P`` / ``Q`` are the
+    exact tables."""
+    rng = np.random.default_rng(2000 + E + seed)
+    d = exact_design(E, seed)
+    n_src, n_dst, F = d["n_src"], d["n_dst"], MODULE_F
+    d["hd"] = rng.integers(-2, 3, size=(n_src, F)).astype(np.float32)
+    d["hs"] = rng.integers(-2, 3, size=(n_dst, F)).astype(np.float32)
+    d["W1"] = (rng.integers(-1, 2, size=(H1, 2 * F)) * (rng.random((H1, 2 * F)) < 0.4)).astype(np.float32)
+    d["b1"] = rng.integers(-1, 2, size=H1).astype(np.float32)
+    P, Q = module_tables(d)
+    d["P"], d["Q"] = P.astype(np.float32), Q.astype(np.float32)
+    assert np.array_equal(d["P"], P) and np.array_equal(d["Q"], Q)
+    return d
+
+
+def module_tables(d, absolute=False):
+    hd, hs, W1, b1 = (np.asarray(d[k], dtype=np.float64) for k in ("hd", "hs", "W1", "b1"))
+    if absolute:
+        hd, hs, W1, b1 = np.abs(hd), np.abs(hs), np.abs(W1), np.abs(b1)
+    F = hd.shape[1]
+    return hd @ W1[:, :F].T + b1, hs @ W1[:, F:].T
+
+
+def module_reference(d, p, seed, absolute=False, g=None, open_gates=False):
+    """The float64 restatement of ``MLPDecoder.forward`` on the fused route: the two ``lin1`` tables, ``reference`` on
+    them, and the chain rule back to ``hd``, ``hs``, ``lin1.weight`` and ``lin1.bias``.  ``absolute=True``: sum|terms| of
+    every stage on the absolute values of ITS operands (the tables' own sums as ``P`` / ``Q``; the gradient stages on
+    the absolute-value ``dP`` / ``dQ``, which bound the true ones)."""
+    P, Q = module_tables(d)
+    r = reference(P, Q, d["W2"], d["b2"], d["w3"], d["b3"], d["src"], d["dst"], p, seed, d["g"] if g is None else g,
+                  absolute=absolute, open_gates=open_gates)
+    hd, hs, W1 = (np.asarray(d[k], dtype=np.float64) for k in ("hd", "hs", "W1"))
+    if absolute:
+        hd, hs, W1 = np.abs(hd), np.abs(hs), np.abs(W1)
+        r["P"], r["Q"] = module_tables(d, absolute=True)
+    F = hd.shape[1]
+    r["dhd"], r["dhs"] = r["dP"] @ W1[:, :F], r["dQ"] @ W1[:, F:]
+    r["dW1"] = np.concatenate([r["dP"].T @ hd, r["dQ"].T @ hs], 1)
+    r["db1"] = r["dP"].sum(0)
+    return r
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# non-finite rows
+NONFINITE_E = 129
+NF_NAN_ONE, NF_NAN_ROW, NF_NEG_INF = 7, 9, 11   # source nodes: NaN in one column, a row of NaN, -Inf in one column
+NF_DST = 4                                      # destination node: +Inf in NF_COL_INF, -Inf in NF_COL_NEG
+NF_COL_NAN, NF_COL_INF, NF_COL_NEG = 17, 22, 21
+
+
+def nonfinite_design(E=NONFINITE_E):
+    """``exact_design(E)`` with non-finite rows.  Source node 7 holds a NaN in column 17, source node 9 is all NaN,
+    destination node 4 holds +Inf in column 22 and -Inf in column 21, source node 11 holds -Inf in column 22: listed
+    against node 4 its column 22 is ``-Inf + Inf = NaN``, against a finite row ``-Inf`` (relu: 0).  Each of them is
+    written into the list at several positions of both waves' halves, so that under one mask the non-finite unit is
+    kept at some positions and dropped at others (asserted on the host).  ``touch``: the positions that name one of
+    these nodes; ``g`` is 0 there.  ``finite``: the same design with the non-finite rows replaced by zeros."""
+    d = exact_design(E)
+    src, dst = d["src"].copy(), d["dst"].copy()
+    dst[dst == NF_DST] = NF_DST + 1
+    for s in (NF_NAN_ONE, NF_NAN_ROW, NF_NEG_INF):
+        src[src == s] = s + 1
+    at = lambda *pos: np.array([q for q in pos if q < E], dtype=np.int64)  # noqa: E731
+    src[at(1, 30, 33, 63, 70, 100, 127, 128)] = NF_NAN_ONE
+    src[at(2, 34, 90)] = NF_NAN_ROW
+    dst[at(3, 31, 35, 64, 65, 96, 110, 120)] = NF_DST
+    both = at(5, 40, 66, 97, 111)
+    src[both], dst[both] = NF_NEG_INF, NF_DST
+    src[at(6, 41)] = NF_NEG_INF
+    P, Q = d["P"].copy(), d["Q"].copy()
+    rows_p, rows_q = [NF_NAN_ONE, NF_NAN_ROW, NF_NEG_INF], [NF_DST]
+    fin = dict(d, src=src, dst=dst, P=P.copy(), Q=Q.copy())
+    fin["P"][rows_p], fin["Q"][rows_q] = 0, 0
+    P[NF_NAN_ONE, NF_COL_NAN] = np.nan
+    P[NF_NAN_ROW] = np.nan
+    P[NF_NEG_INF, NF_COL_INF] = -np.inf
+    Q[NF_DST, NF_COL_INF], Q[NF_DST, NF_COL_NEG] = np.inf, -np.inf
+    touch = np.isin(src, rows_p) | np.isin(dst, rows_q)
+    g = np.where(touch, 0, d["g"]).astype(np.float32)
+    fin["g"] = g
+    return dict(d, P=P, Q=Q, src=src, dst=dst, g=g, touch=touch, finite=fin)
 
 
 def float_design(E=5000, seed=7, settle=None):

@@ -1,7 +1,9 @@
 """The fused training decoder, host side (no GPU): include/dgmi_train.h declares exactly the new entry points, the
 library exports them and ``TRAIN_SIGNATURES`` matches type for type; argument validation and workspace sizing return
 codes before any launch; the numpy restatement of the dropout mask has the statistics a mask needs (share, independence
-of the layers, of sequential seeds and of translated seeds); the exact designs are exact."""
+of the layers, of sequential seeds and of translated seeds); the exact designs are exact; the ``select`` form of the
+restatement is the product form's bits on finite designs; the module design is exact under every seed; the non-finite
+design keeps and drops its units under the test mask; the mask's extremes (p next to 0 and next to 1, negative seeds)."""
 import ctypes
 import math
 import os
@@ -220,3 +222,161 @@ def test_exact_designs_are_exact_and_have_their_special_nodes_and_units(E):
         assert len(np.unique(pairs, axis=0)) < E                                     # duplicated pairs
     if E == 40_000:
         assert np.sum(src == 0) >= 3000
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the two forms of the restatement, the module design, the non-finite design, the mask's extremes
+def _same(a, b, keys):
+    for k in keys:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+
+
+OUTPUTS = ("logit", "z2", "dz1") + K.GRADS
+
+
+@pytest.mark.parametrize("E", K.EXACT_SIZES)
+def test_select_and_product_forms_are_the_same_bits_on_the_integer_designs(E):
+    d = K.exact_design(E)
+    for p in (0.5, 0.0):
+        for absolute in (False, True):
+            _same(K.ref_of(d, p, SEED, form="select", absolute=absolute), K.ref_of(d, p, SEED, absolute=absolute), OUTPUTS)
+
+
+@pytest.mark.parametrize("design", ["float-5000-settled", "float-129", "float-40000", "module-33", "module-385"])
+def test_select_and_product_forms_are_the_same_bits_on_the_other_finite_designs(design):
+    kind, E = design.split("-")[0], int(design.split("-")[1])
+    p = 0.3 if kind == "float" else 0.5
+    if kind == "module":
+        d = K.module_design(E)
+    else:
+        d = K.float_design(E, settle=(p, SEED)) if design.endswith("settled") else K.float_design(E, seed=21 if E > 129 else E)
+    for absolute in (False, True):
+        _same(K.ref_of(d, p, SEED, form="select", absolute=absolute), K.ref_of(d, p, SEED, absolute=absolute), OUTPUTS)
+
+
+@pytest.mark.parametrize("E", [33, 385])
+def test_module_designs_are_exact_under_every_seed(E):
+    """The condition of the exact module test: sum|terms| of the two lin1 tables, of every output of the fused op and of
+    the four gradients behind the tables, with EVERY gate open (the GPU test draws its seed on the device)."""
+    d = K.module_design(E)
+    for p in (0.5, 0.0):
+        assert K.exact_margin(d, p, None) < 2 ** 24
+        assert K.exact_margin(d, p, SEED) <= K.exact_margin(d, p, None)
+    for k in ("hd", "hs", "W1", "b1", "W2", "b2", "w3", "b3", "g"):   # bf16 numbers: a GEMM may round its inputs
+        t = torch.from_numpy(d[k])
+        assert torch.equal(t.bfloat16().float(), t), k
+    r, P = K.module_reference(d, 0.5, SEED), K.module_tables(d)
+    assert np.array_equal(d["P"], P[0]) and np.array_equal(d["Q"], P[1]) and d["P"].dtype == np.float32
+    assert r["dW1"].shape == d["W1"].shape and r["db1"].shape == d["b1"].shape and r["dhd"].shape == d["hd"].shape
+    assert all(np.any(r[k]) for k in K.MODULE_GRADS) or E < 33
+    # the chain rule against float64 autograd of the same expression
+    t = {k: torch.from_numpy(d[k]).double().requires_grad_(k in ("hd", "hs", "W1", "b1")) for k in ("hd", "hs", "W1", "b1")}
+    Pt = t["hd"] @ t["W1"][:, :K.MODULE_F].t() + t["b1"]
+    Qt = t["hs"] @ t["W1"][:, K.MODULE_F:].t()
+    (Pt * torch.from_numpy(r["dP"])).sum().backward(retain_graph=True)
+    (Qt * torch.from_numpy(r["dQ"])).sum().backward()
+    for k, name in (("hd", "dhd"), ("hs", "dhs"), ("W1", "dW1"), ("b1", "db1")):
+        assert np.array_equal(t[k].grad.numpy(), r[name]), name
+    src = d["src"]
+    assert not np.any(src == 1) and np.sum(src == 0) >= E // 4 and len(np.unique(np.stack([src, d["dst"]], 1), axis=0)) < E
+
+
+def test_upstream_gradient_of_ones_keeps_the_integer_design_exact():
+    d = K.exact_design(385)
+    assert K.exact_margin(d, 0.5, SEED, g=np.ones(385)) < 2 ** 24
+
+
+def test_nonfinite_design_keeps_and_drops_its_units_under_the_test_mask():
+    d = K.nonfinite_design()
+    E, src, dst, touch = K.NONFINITE_E, d["src"], d["dst"], d["touch"]
+    m1, _ = K.masks(SEED, E, 0.5)
+    one = np.nonzero(src == K.NF_NAN_ONE)[0]
+    row = np.nonzero(src == K.NF_NAN_ROW)[0]
+    inf = np.nonzero((dst == K.NF_DST) & (src != K.NF_NEG_INF))[0]
+    clash = np.nonzero((dst == K.NF_DST) & (src == K.NF_NEG_INF))[0]
+    low = np.nonzero((dst != K.NF_DST) & (src == K.NF_NEG_INF))[0]
+    assert len(one) >= 8 and len(row) >= 3 and len(inf) >= 8 and len(clash) >= 5 and len(low) >= 2
+    assert np.isnan(d["P"][K.NF_NAN_ONE]).sum() == 1 and np.isnan(d["P"][K.NF_NAN_ROW]).all()
+    assert d["Q"][K.NF_DST, K.NF_COL_INF] == np.inf and d["Q"][K.NF_DST, K.NF_COL_NEG] == -np.inf
+    assert np.isfinite(d["Q"]).sum() == d["Q"].size - 2 and d["P"][K.NF_NEG_INF, K.NF_COL_INF] == -np.inf
+    assert touch.sum() == len(one) + len(row) + len(inf) + len(clash) + len(low) and not d["g"][touch].any()
+    assert d["g"][~touch].any() and np.isfinite(d["finite"]["P"]).all() and np.isfinite(d["finite"]["Q"]).all()
+    assert K.exact_margin(d["finite"], 0.5, SEED) < 2 ** 24 and K.exact_margin(d["finite"], 0.0, SEED) < 2 ** 24
+    # kept at some positions, dropped at others
+    for pos, col in ((one, K.NF_COL_NAN), (inf, K.NF_COL_INF), (clash, K.NF_COL_INF)):
+        assert m1[pos, col].any() and not m1[pos, col].all(), (pos, col)
+    r = K.ref_of(d, 0.5, SEED, form="select")
+    logit = r["logit"]
+    assert np.array_equal(np.isnan(logit[one]), m1[one, K.NF_COL_NAN])         # finite exactly where the NaN is dropped
+    assert np.array_equal(np.isfinite(logit[inf]), ~m1[inf, K.NF_COL_INF])    # kept +Inf: 0 * Inf or Inf - Inf in z2
+    assert np.array_equal(np.isnan(logit[clash]), m1[clash, K.NF_COL_INF])    # Inf - Inf = NaN in z1 itself
+    assert np.isnan(logit[row]).all() and np.isfinite(logit[low]).all()       # relu(-Inf + finite) = 0
+    assert np.isfinite(logit[~touch]).all()
+    # a pair of two finite nodes: the bits of the design with the non-finite rows zeroed; dz1 is finite everywhere
+    f = K.ref_of(d["finite"], 0.5, SEED, form="select")
+    assert np.array_equal(logit[~touch], f["logit"][~touch]) and np.array_equal(r["dz1"], f["dz1"])
+    assert np.isfinite(r["dz1"]).all() and not r["dz1"][touch].any()
+    for k in ("dP", "dQ", "db2", "db3"):
+        assert np.array_equal(r[k], f[k]), k
+    # numpy's product does what the contract says of the sums: 0 * NaN is NaN (column k of dW2, entry h of dw3)
+    with np.errstate(invalid="ignore"):
+        s, g = 2.0, d["g"].astype(np.float64)
+        z1 = d["P"].astype(np.float64)[src] + d["Q"].astype(np.float64)[dst]
+        h1 = np.where(m1, np.maximum(z1, 0.0) * s, 0.0)
+    bad_k = ~np.isfinite(h1).all(0)
+    assert bad_k[K.NF_COL_NAN] and bad_k[K.NF_COL_INF] and not bad_k.all()  # the all-NaN row is dropped in some columns
+    assert np.array_equal(np.isnan(r["dW2"]), np.broadcast_to(bad_k, (64, 128)))
+    _, m2 = K.masks(SEED, E, 0.5)
+    with np.errstate(invalid="ignore"):
+        bad_h = ~np.isfinite(np.where(m2, np.maximum(r["z2"], 0.0) * s, 0.0)).all(0)
+    assert bad_h.any() and np.array_equal(np.isnan(r["dw3"]), bad_h) and g[~touch].any()
+    print("dW2 columns NaN: %d of 128, dw3 entries NaN: %d of 64" % (bad_k.sum(), bad_h.sum()))
+    # the product form, which is the torch chain's, differs: a dropped NaN stays NaN
+    prod = K.ref_of(d, 0.5, SEED)["logit"]
+    assert np.isnan(prod[one]).all() and not np.array_equal(np.isnan(prod), np.isnan(logit))
+
+
+def test_mask_extremes_on_the_host():
+    E = 129
+    # p = 2^-24: thr = 0xFFFFFF00, scale 1 + 2^-23; p = 1e-12 and p just below 2^-33: thr = 2^32 - 1 (NOT 2^32: only a unit
+    # whose hash is 0xFFFFFFFF goes), scale exactly 1, and under the test seed every unit of 129 pairs is kept
+    assert K.threshold(2.0 ** -24) == 0xFFFFFF00 and K.scale(2.0 ** -24) == np.float32(1.0 + 2.0 ** -23)
+    for p in (1e-12, float(np.nextafter(np.float32(2.0 ** -33), np.float32(0)))):
+        assert K.threshold(p) == 2 ** 32 - 1 and K.scale(p) == np.float32(1.0)
+        assert all(m.all() for m in K.masks(SEED, E, p))
+    assert K.threshold(2.0 ** -60) == 2 ** 32                    # 1 - p is 1.0 in double: the "keep all" branch
+    m1, m2 = K.masks(SEED, E, 2.0 ** -24)
+    assert m1.all() and m2.all()                                 # 256 / 2^32 per unit: nothing goes at this size either
+    # p = 0.999 and p = 1 - 2^-10 (scale exactly 1024): most pairs lose a whole layer
+    assert K.scale(1.0 - 2.0 ** -10) == np.float32(1024.0) and K.threshold(1.0 - 2.0 ** -10) == 2 ** 22
+    assert float(np.float32(1.0 - 2.0 ** -10)) == 1.0 - 2.0 ** -10
+    assert K.scale(0.999) != np.float32(1000.0)
+    for p in (0.999, 1.0 - 2.0 ** -10):
+        for n, both in ((129, 0), (385, 1)):
+            m1, m2 = K.masks(SEED, n, p)
+            assert (~m2.any(1)).sum() >= 1 and (~m1.any(1)).sum() >= 1
+            # at 129 pairs NO position keeps a unit in both layers under this seed (expected: 0.97 positions); at 385 one does
+            assert (m1.any(1) & m2.any(1)).sum() == both, (p, n)
+            assert m1.any() and m2.any()
+    for n in (129, 385):                                         # the integer design at scale 1024, under the test seed
+        assert K.exact_margin(K.exact_design(n), 1.0 - 2.0 ** -10, SEED) < 2 ** 24
+
+
+def test_negative_seeds_are_their_two_complement_cast():
+    """``(uint64_t)seed`` of the kernels: -1 is 2^64 - 1, -2^63 is 2^63; the five seeds of the device probes give five
+    different masks with the share a mask needs."""
+    for layer in (1, 2):
+        assert K.layer_key(-1, layer) == K.layer_key(2 ** 64 - 1, layer) == K.mix64((K.mix64(2 ** 64 - 1) + layer) & K.M64)
+        assert K.layer_key(-2 ** 63, layer) == K.layer_key(2 ** 63, layer)
+        assert K.layer_key(0, layer) == K.mix64((K.mix64(0) + layer) & K.M64)
+        assert len({K.layer_key(s, layer) for s in (SEED, 0, -1, -2 ** 63, 2 ** 63 - 1)}) == 5
+    seen = []
+    for s in (SEED, 0, -1, -2 ** 63, 2 ** 63 - 1):
+        m1, m2 = K.masks(s, 129, 0.3)
+        assert _within(m1.mean(), 0.7, m1.size) and _within(m2.mean(), 0.7, m2.size)
+        assert m2.any(1).all()
+        seen.append(m1)
+    agree = P_DROP ** 2 + (1 - P_DROP) ** 2
+    for i in range(5):
+        for j in range(i):
+            assert _within((seen[i] == seen[j]).mean(), agree, seen[i].size)

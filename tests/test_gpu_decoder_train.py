@@ -2,6 +2,8 @@
 the restated one; with p = 0 the logits are the list scorer's bits; on integer designs every output EQUALS the float64
 restatement; random operands meet the elementwise bar; the module route matches the torch chain; gradients are the same
 bits from run to run; autograd keeps nothing per pair; empty and bad input; HIP-graph capture draws a new mask per replay.
+The module route WITH dropout, ids out of range, non-finite rows and the operand / gradient forms:
+``test_gpu_decoder_train_forms.py``.
 
 Measured on an MI355X (float parity, E = 5000, p = 0.3), worst |err| / (1e-5 sum|terms|): see DESIGN.md 4.15."""
 import numpy as np
@@ -43,17 +45,24 @@ def _run(d, dev, p, seed):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # mask and p = 0 identity
-def test_device_mask_equals_the_restatement(dev):
-    """One-hot operands at E = 129, p = 0.3: with W2 = 0, b2 = 1, w3 = e_h the logit is scale * m2[e, h]; with P = 1,
-    Q = 0, W2[:, k] = 1 (other columns 0), b2 = 0, w3 = 1 it is scale^2 * m1[e, k] * (kept layer-2 units of e)."""
+MASK_CASES = [(0.3, SEED, 129), (0.999, SEED, 129), (2.0 ** -24, SEED, 129), (1e-12, SEED, 129), (0.3, 0, 129), (0.3, -1, 129),
+              (0.3, -2 ** 63, 129), (0.3, 2 ** 63 - 1, 129), (0.999, SEED, 385)]
+
+
+@pytest.mark.parametrize("p,seed_value,E", MASK_CASES, ids=lambda v: "%g" % v if isinstance(v, float) else str(v))
+def test_device_mask_equals_the_restatement(dev, p, seed_value, E):
+    """One-hot operands: with W2 = 0, b2 = 1, w3 = e_h the logit is scale * m2[e, h]; with P = 1, Q = 0, W2[:, k] = 1
+    (other columns 0), b2 = 0, w3 = 1 it is scale^2 * m1[e, k] * (kept layer-2 units of e).  E = 129, p = 0.3 under five
+    seeds (0, negative ones and both ends of int64: the kernels cast to uint64); under the first seed also p = 0.999
+    (most pairs lose a whole layer; at 385 pairs one keeps a unit in both, at 129 none does: test_decoder_train_host.py),
+    p = 2^-24 (thr = 0xFFFFFF00, scale 1 + 2^-23) and p = 1e-12 (thr = 2^32 - 1, scale 1: every unit kept)."""
     from dream_gnn_amd import ops
 
-    E, p = 129, 0.3
     rng = np.random.default_rng(3)
     src, dst = torch.from_numpy(rng.integers(0, 5, E)).to(dev), torch.from_numpy(rng.integers(0, 4, E)).to(dev)
     pairs = ops.EdgePairs(src, dst, 5, 4)
-    seed = _seed(dev)
-    m1, m2 = K.masks(SEED, E, p)
+    seed = _seed(dev, seed_value)
+    m1, m2 = K.masks(seed_value, E, p)
     s = float(K.scale(p))
     P, Q = torch.ones(5, 128, device=dev), torch.zeros(4, 128, device=dev)
     zero, one = torch.zeros(64, device=dev), torch.ones(64, device=dev)
@@ -65,9 +74,32 @@ def test_device_mask_equals_the_restatement(dev):
         got1 = torch.stack([ops.pair_mlp_train(P, Q, cols[k].expand(64, 128).contiguous(), zero, one, b3, pairs, p, seed=seed)
                             for k in range(128)], 1).cpu().numpy()
     assert np.array_equal(got2, m2 * np.float32(s))
-    assert m2.any(1).all()  # every pair keeps a layer-2 unit, so layer 1 shows through
-    assert np.array_equal(got1 != 0, m1) and np.all(got1 >= 0)
-    assert not m1.all() and not m2.all() and m1.any() and m2.any()
+    shows = m2.any(1)  # a pair that keeps a layer-2 unit shows its layer 1
+    if p <= 0.3:
+        assert shows.all()
+    assert np.array_equal(got1 != 0, m1 & shows[:, None]) and np.all(got1 >= 0)
+    if p == 0.3:
+        assert not m1.all() and not m2.all() and m1.any() and m2.any()
+    elif p < 0.3:
+        assert m1.all() and m2.all()
+        if s == 1.0:
+            assert np.all(got1 == 64.0)
+    else:
+        assert (~shows).any() and (~m1.any(1)).any() and m1.any() and m2.any()
+        assert bool((m1.any(1) & shows).any()) == (E == 385)
+
+
+def test_p_one_hash_step_above_zero_is_the_p_zero_bits(dev):
+    """p = 1e-12: every unit of the 129 pairs is kept (host test) and the scale is exactly 1, through the masked path."""
+    from dream_gnn_amd import ops
+
+    d = K.float_design(129, seed=129)
+    t, pairs, _ = _dev(d, dev)
+    assert all(m.all() for m in K.masks(SEED, 129, 1e-12)) and K.scale(1e-12) == np.float32(1.0) and K.threshold(1e-12) < 2 ** 32
+    with torch.no_grad():
+        got = ops.pair_mlp_train(*t, pairs, 1e-12, seed=_seed(dev))
+        assert torch.equal(got, ops.pair_mlp_train(*t, pairs, 0.0, seed=_seed(dev)))
+    assert torch.equal(got, ops.pair_mlp_score_list(*t, pairs.src, pairs.dst))
 
 
 @pytest.mark.parametrize("E", [1, 31, 32, 33, 127, 128, 129, 385, 40_000])
