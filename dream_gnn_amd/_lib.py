@@ -142,6 +142,15 @@ TRAIN_SIGNATURES = {
                                                                           ctypes.c_size_t, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/dgmi_attn.h (its own table, for the same reason).
+_ATTN_OPERANDS = [_vp, _i64, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]
+ATTN_SIGNATURES = {
+    "dgmi_attn_fuse_workspace_bytes": (ctypes.c_size_t, [_i64, ctypes.c_int32]),
+    "dgmi_attn_fuse_forward_f32": (ctypes.c_int, _ATTN_OPERANDS + [_vp, _i64, _vp, _vp]),
+    "dgmi_attn_fuse_backward_f32": (ctypes.c_int, _ATTN_OPERANDS + [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                                                     ctypes.c_size_t, _vp]),
+}
+
 
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
@@ -156,8 +165,9 @@ def _load() -> ctypes.CDLL:
     for name, (res, args) in (list(SIGNATURES.items()) + list(PAIR_SIGNATURES.items()) + list(RANK_SIGNATURES.items())
                               + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
                               + list(GIVEN_SIGNATURES.items()) + list(CURVE_SIGNATURES.items())
-                              + list(LAYOUT_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the nine headers declare
+                              + list(LAYOUT_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
+                              + list(ATTN_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the ten headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()

@@ -26,6 +26,7 @@
 
 #include "dgmi.h"
 #include "dgmi_above.h"
+#include "dgmi_attn.h"
 #include "dgmi_bf16.h"
 #include "dgmi_curve.h"
 #include "dgmi_given.h"
@@ -83,7 +84,7 @@ Tensor scratch(const Tensor& like, size_t nbytes, int kind) {
   }
   return it->second;
 }
-enum { kPartials = 0, kPlanes = 1, kBuilder = 2, kPairs = 3, kTrain = 4 };
+enum { kPartials = 0, kPlanes = 1, kBuilder = 2, kPairs = 3, kTrain = 4, kAttn = 5 };
 
 struct Keep {
   const int32_t* eid = nullptr;
@@ -730,6 +731,86 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> pair_mlp_train_backwa
   return {dz1, dW2, db2, dw3, db3, info};
 }
 
+// the two-channel attention fusion in training (dgmi_attn.hip): out = beta'_0 A + beta'_1 B with beta = softmax over the two
+// channels of w2 . tanh(W1 z + b1) and M the caller's (n, 2) dropout factors, and every gradient from a recompute.  A and
+// B are consumed in place by leading dimension (the two halves z[:, 0] / z[:, 1] of a stacked (n, 2, F) tensor included);
+// when they ARE such halves the backward writes dA / dB as the halves of one (n, 2, F) tensor.  The backward's workspace
+// (the workgroups' partial sums) is the per-(device, stream) scratch; nothing here synchronises, so both ops can be captured.
+struct AttnOperands {
+  Dense a, b;
+  Tensor W1, b1, w2, M;
+  const float* m = nullptr;
+};
+
+AttnOperands attn_operands(const Tensor& A, const Tensor& B, const OptTensor& M, const Tensor& W1, const Tensor& b1, const Tensor& w2) {
+  AttnOperands o;
+  o.a = dense16_of(A, "A");
+  o.b = dense16_of(B, "B");
+  TORCH_CHECK(B.device() == A.device(), "tensors on different devices: B on ", B.device().str(), " vs ", A.device().str());
+  TORCH_CHECK(o.a.rows == o.b.rows && o.a.F == o.b.F, "A and B must have one shape, got (", o.a.rows, ", ", o.a.F, ") and (",
+              o.b.rows, ", ", o.b.F, ")");
+  TORCH_CHECK(o.a.F >= 4 && o.a.F <= 512 && o.a.F % 4 == 0, "the width must be a multiple of 4 in [4, 512], got ", o.a.F);
+  TORCH_CHECK(o.a.rows <= (int64_t)INT32_MAX, "at most 2^31 - 1 rows");
+  check(W1, at::kFloat, 2, "W1", A);
+  TORCH_CHECK(W1.size(0) == 16 && W1.size(1) == o.a.F, "W1 must be (16, ", o.a.F, "), got (", W1.size(0), ", ", W1.size(1), ")");
+  check(b1, at::kFloat, 1, "b1", A);
+  check(w2, at::kFloat, 1, "w2", A);
+  TORCH_CHECK(b1.numel() == 16 && w2.numel() == 16, "b1 / w2 must have 16 entries");
+  o.W1 = contiguous16(W1), o.b1 = b1, o.w2 = w2;
+  if (M.has_value() && M->defined()) {
+    check(*M, at::kFloat, 2, "M", A);
+    TORCH_CHECK(M->size(0) == o.a.rows && M->size(1) == 2, "M must be (", o.a.rows, ", 2)");
+    o.M = *M;
+    o.m = o.M.data_ptr<float>();
+  }
+  return o;
+}
+
+std::tuple<Tensor, Tensor> attn_fuse_forward(const Tensor& A, const Tensor& B, const OptTensor& M, const Tensor& W1,
+                                             const Tensor& b1, const Tensor& w2) {
+  AttnOperands o = attn_operands(A, B, M, W1, b1, w2);
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(o.a.t.device());
+  auto opts = o.a.t.options().dtype(at::kFloat);
+  Tensor out = at::empty({o.a.rows, o.a.F}, opts), beta = at::empty({o.a.rows, 2}, opts);
+  if (o.a.rows == 0) return {out, beta};
+  check_status(dgmi_attn_fuse_forward_f32(o.a.t.data_ptr<float>(), o.a.ld, o.b.t.data_ptr<float>(), o.b.ld, o.a.rows, (int32_t)o.a.F,
+                                          16, o.W1.data_ptr<float>(), o.b1.data_ptr<float>(), o.w2.data_ptr<float>(), o.m,
+                                          out.data_ptr<float>(), o.a.F, beta.data_ptr<float>(), stream_of(o.a.t)),
+               "dgmi_attn_fuse_forward_f32");
+  return {out, beta};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> attn_fuse_backward(const Tensor& A, const Tensor& B, const OptTensor& M,
+                                                                      const Tensor& W1, const Tensor& b1, const Tensor& w2,
+                                                                      const Tensor& dout) {
+  AttnOperands o = attn_operands(A, B, M, W1, b1, w2);
+  Dense g = dense16_of(dout, "dout");
+  TORCH_CHECK(dout.device() == A.device(), "tensors on different devices: dout on ", dout.device().str(), " vs ", A.device().str());
+  TORCH_CHECK(g.rows == o.a.rows && g.F == o.a.F, "dout must be (", o.a.rows, ", ", o.a.F, "), got (", g.rows, ", ", g.F, ")");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(o.a.t.device());
+  auto opts = o.a.t.options().dtype(at::kFloat);
+  const int64_t n = o.a.rows, F = o.a.F;
+  Tensor dA, dB;
+  int64_t ldd = F;
+  if (n > 0 && o.a.ld == 2 * F && o.b.ld == 2 * F && o.b.t.data_ptr<float>() == o.a.t.data_ptr<float>() + F) {
+    Tensor dz = at::empty({n, 2, F}, opts);  // the halves of one stacked tensor: one dz, no stack in the caller
+    dA = dz.select(1, 0), dB = dz.select(1, 1), ldd = 2 * F;
+  } else {
+    dA = at::empty({n, F}, opts), dB = at::empty({n, F}, opts);
+  }
+  if (n == 0) return {dA, dB, at::zeros({16, F}, opts), at::zeros({16}, opts), at::zeros({16}, opts)};
+  Tensor dW1 = at::empty({16, F}, opts), db1 = at::empty({16}, opts), dw2 = at::empty({16}, opts);
+  const size_t wbytes = dgmi_attn_fuse_workspace_bytes(n, (int32_t)F);
+  Tensor ws = scratch(o.a.t, wbytes < 256 ? 256 : wbytes, kAttn);
+  check_status(dgmi_attn_fuse_backward_f32(o.a.t.data_ptr<float>(), o.a.ld, o.b.t.data_ptr<float>(), o.b.ld, n, (int32_t)F, 16,
+                                           o.W1.data_ptr<float>(), o.b1.data_ptr<float>(), o.w2.data_ptr<float>(), o.m,
+                                           g.t.data_ptr<float>(), g.ld, dA.data_ptr<float>(), ldd, dB.data_ptr<float>(), ldd,
+                                           dW1.data_ptr<float>(), db1.data_ptr<float>(), dw2.data_ptr<float>(), ws.data_ptr(),
+                                           (size_t)ws.numel(), stream_of(o.a.t)),
+               "dgmi_attn_fuse_backward_f32");
+  return {dA, dB, dW1, db1, dw2};
+}
+
 // exact AUROC / AUPR of scored samples, overall (n_segments = 0) or per segment (dgmi_curve.hip): count = (S, 6) int64
 // rows (P, N, TP at the threshold, FP at the threshold, groups, U2), area = (S, 2) float64 rows (auroc, aupr), info =
 // [flag word] (bit 0 NaN score, bit 1 label not 0 / 1, bit 2 segment id out of range).  Any shape of score (flattened);
@@ -1200,6 +1281,16 @@ TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, train) {
 TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, train) {
   train.impl("pair_mlp_train_forward", pair_mlp_train_forward);
   train.impl("pair_mlp_train_backward", pair_mlp_train_backward);
+}
+
+TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, attn) {
+  attn.def("attn_fuse_forward(Tensor A, Tensor B, Tensor? M, Tensor W1, Tensor b1, Tensor w2) -> (Tensor, Tensor)");
+  attn.def("attn_fuse_backward(Tensor A, Tensor B, Tensor? M, Tensor W1, Tensor b1, Tensor w2, Tensor dout) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(dreamgnn_mi, CUDA, attn) {
+  attn.impl("attn_fuse_forward", attn_fuse_forward);
+  attn.impl("attn_fuse_backward", attn_fuse_backward);
 }
 
 TORCH_LIBRARY_FRAGMENT(dreamgnn_mi, metrics) {

@@ -21,15 +21,57 @@ from .layers import FGCN, GCMCLayer, get_activation
 class Attention(nn.Module):
     """Two-way softmax attention over stacked embeddings — layers.py:324-338."""
 
-    def __init__(self, in_size, hidden_size=16, dropout_rate=0.1):
+    #: Opt-in: the whole chain as ONE HIP kernel forward and a recompute backward (``ops.attention_fuse``, DESIGN.md
+    #: 4.16) when the operands are fusable: fp32 HIP tensors, exactly two channels, a width that is a multiple of 4 in
+    #: [4, 512], rows with unit inner stride on 16-byte boundaries, and the ``project`` the constructor made.  Anything
+    #: else takes the torch chain.  With the flag on, the returned ``beta`` carries NO gradient (the kernels return the
+    #: weights after dropout as a constant); ``out`` is differentiable in the inputs and the three parameters.
+    fused = False
+
+    def __init__(self, in_size, hidden_size=16, dropout_rate=0.1, fused=False):
         super().__init__()
+        if fused:
+            self.fused = True
         self.project = nn.Sequential(nn.Linear(in_size, hidden_size), nn.Tanh(),
                                      nn.Linear(hidden_size, 1, bias=False))
         self.dropout = nn.Dropout(dropout_rate)
 
     def forward(self, z):
+        if self.fused and z.dim() == 3 and z.shape[1] == 2 and self._fusable(z[:, 0], z[:, 1]):
+            return self._fused(z, None)
         beta = self.dropout(torch.softmax(self.project(z), dim=1))
         return (beta * z).sum(1), beta
+
+    def fuse(self, a, b):
+        """``self.forward(torch.stack([a, b], 1))``; with ``fused`` set and fusable operands the two tables go to the
+        kernel as they are, so the stack is never made.  Returns ``(out, beta)``, ``beta`` of shape ``(n, 2, 1)``; on
+        the fused route ``beta`` (the weights after dropout) carries no gradient."""
+        if self.fused and a.dim() == 2 and a.shape == b.shape and self._fusable(a, b):
+            return self._fused(a, b)
+        return self.forward(torch.stack([a, b], dim=1))
+
+    def _fusable(self, a, b):
+        p = self.project
+        if not (isinstance(p, nn.Sequential) and len(p) == 3 and isinstance(p[0], nn.Linear) and isinstance(p[1], nn.Tanh)
+                and isinstance(p[2], nn.Linear) and p[0].bias is not None and p[2].bias is None):
+            return False
+        F_ = a.shape[1]
+        if p[0].weight.shape != (16, F_) or p[2].weight.shape != (1, 16) or F_ % 4 != 0 or not 4 <= F_ <= 512:
+            return False
+        for t in (a, b):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.stride(1) == 1 and t.stride(0) % 4 == 0
+                    and t.stride(0) >= F_ and t.data_ptr() % 16 == 0):
+                return False
+        return all(w.is_cuda and w.dtype == torch.float32 for w in (p[0].weight, p[0].bias, p[2].weight))
+
+    def _fused(self, a, b):
+        n = a.shape[0]
+        mult = None
+        if self.training and 0.0 < self.dropout.p:
+            # the draw nn.Dropout would make on beta (n, 2, 1): the same mask and the same generator state afterwards
+            mult = F.dropout(torch.ones(n, 2, 1, device=a.device), self.dropout.p, True).view(n, 2)
+        out, beta = ops.attention_fuse(a, b, self.project[0].weight, self.project[0].bias, self.project[2].weight, mult)
+        return out, beta.view(n, 2, 1)
 
 
 def _split_k_weight_grad(dy, x, chunk: int):
@@ -471,8 +513,8 @@ class Net(nn.Module):
 
         drug_sim_out, dis_sim_out, *_ = self.FGCN(drug_graph, drug_sim_feat, dis_graph, disease_sim_feat,
                                                   drug_feature_graph, disease_feature_graph)
-        drug_feats, _ = self.attention(torch.stack([drug_out, drug_sim_out], dim=1))
-        dis_feats, _ = self.attention(torch.stack([dis_out, dis_sim_out], dim=1))
+        drug_feats, _ = self.attention.fuse(drug_out, drug_sim_out)
+        dis_feats, _ = self.attention.fuse(dis_out, dis_sim_out)
         return drug_feats, dis_feats, drug_out, drug_sim_out, dis_out, dis_sim_out
 
 

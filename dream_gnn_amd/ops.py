@@ -1486,6 +1486,89 @@ def pair_mlp_train(P: torch.Tensor, Q: torch.Tensor, W2: torch.Tensor, b2: torch
 pair_mlp_train.last_seed = None
 
 
+#: rows of one block and the largest grid of the attention kernels (``DGMI_ATTN_BLOCK_ROWS`` / ``DGMI_ATTN_MAX_WORKGROUPS``
+#: of ``include/dgmi_attn.h``): block ``b`` belongs to workgroup ``b mod grid``, which fixes the order of the parameter sums
+ATTN_FUSE_BLOCK_ROWS = 64
+ATTN_FUSE_MAX_WORKGROUPS = 1024
+_ATTN_HIDDEN = 16
+
+
+class _AttentionFuse(torch.autograd.Function):
+    """The two-channel attention fusion (``dgmi_attn.hip``).  Forward: one kernel; saves its inputs and nothing else.
+    Backward: a recompute kernel and a fixed-order reduce.  ``b is None``: ``a`` is the stacked ``(n, 2, F)`` tensor, its
+    two halves go to the kernels by leading dimension ``2 F`` and the backward writes both halves of one ``dz``."""
+
+    @staticmethod
+    def forward(ctx, a, b, W1, b1, w2, mult):
+        A, B = (a[:, 0], a[:, 1]) if b is None else (a, b)
+        out, beta = _T.attn_fuse_forward(A, B, mult, W1, b1.reshape(-1), w2.reshape(-1))
+        ctx.stacked = b is None
+        ctx.save_for_backward(a, b, W1, b1, w2, mult)
+        ctx.mark_non_differentiable(beta)
+        return out, beta
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dbeta):
+        a, b, W1, b1, w2, mult = ctx.saved_tensors
+        A, B = (a[:, 0], a[:, 1]) if ctx.stacked else (a, b)
+        dA, dB, dW1, db1, dw2 = _T.attn_fuse_backward(A, B, mult, W1, b1.reshape(-1), w2.reshape(-1), dout)
+        need = ctx.needs_input_grad
+        if ctx.stacked:
+            n, F = dA.shape
+            if n > 0 and dA.stride(0) == 2 * F and dB.data_ptr() == dA.data_ptr() + 4 * F:
+                da = dA.as_strided((n, 2, F), (2 * F, F, 1))  # the op wrote the two halves of one tensor
+            else:  # the op copied a misaligned view (or n = 0): two tables came back
+                da = torch.stack([dA, dB], 1)
+            db = None
+        else:
+            da, db = dA, dB
+        return (da if need[0] else None, db if need[1] else None, dW1 if need[2] else None,
+                db1.reshape(b1.shape) if need[3] else None, dw2.reshape(w2.shape) if need[4] else None, None)
+
+
+def _check_attention(A, B, W1, b1, w2, mult):
+    if A.dim() != 2 or B.dim() != 2 or A.shape != B.shape:
+        raise ValueError("a and b must be two (n, F) tables of one shape, got %s and %s" % (tuple(A.shape), tuple(B.shape)))
+    n, F = A.shape
+    if F % 4 != 0 or not 4 <= F <= 512:
+        raise ValueError("the width must be a multiple of 4 in [4, 512], got %d" % F)
+    if W1.dim() != 2 or W1.shape[0] != _ATTN_HIDDEN or b1.numel() != _ATTN_HIDDEN or w2.numel() != _ATTN_HIDDEN:
+        raise ValueError("only hidden size %d is supported: W1 %s, b1 %s, w2 %s"
+                         % (_ATTN_HIDDEN, tuple(W1.shape), tuple(b1.shape), tuple(w2.shape)))
+    if W1.shape[1] != F:
+        raise ValueError("W1 must be (%d, %d), got %s" % (_ATTN_HIDDEN, F, tuple(W1.shape)))
+    if mult is not None and tuple(mult.shape) != (n, 2):
+        raise ValueError("mult must be (%d, 2), got %s" % (n, tuple(mult.shape)))
+    for name, t in (("a", A), ("b", B), ("W1", W1), ("b1", b1), ("w2", w2), ("mult", mult)):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (name, t.dtype))
+
+
+def attention_fuse(a: torch.Tensor, b: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                   mult: Optional[torch.Tensor] = None):
+    """``(out, beta)`` of the encoder's two-channel attention fusion, one HIP kernel (``include/dgmi_attn.h``)::
+
+        s_c = w2 . tanh(W1 z_c + b1),  beta = softmax(s_0, s_1) * mult[n],  out[n] = beta_0 a[n] + beta_1 b[n]
+
+    ``a``, ``b``: ``(n, F)`` fp32, ``F`` a multiple of 4 in [4, 512], rows contiguous (row-strided views are consumed in
+    place); ``W1`` ``(16, F)``, ``b1`` and ``w2`` 16 entries; ``mult`` an optional ``(n, 2)`` multiplier (the dropout
+    factors of the two weights; a constant).  ``b=None`` takes ``a`` as the stacked ``(n, 2, F)`` tensor.  ``out`` is
+    ``(n, F)``, ``beta`` ``(n, 2)`` (after the multiplier) and NOT differentiable.  Differentiable once in ``a``, ``b``,
+    ``W1``, ``b1``, ``w2``: the backward recomputes the hidden layer and the softmax, autograd keeps the inputs only, and
+    every sum is free of float atomics (bit-identical from run to run).  Nothing here synchronises."""
+    _require_device(a, b, W1, b1, w2, mult)
+    if mult is not None and not mult.is_contiguous():
+        mult = mult.contiguous()
+    if b is None:
+        if a.dim() != 3 or a.shape[1] != 2:
+            raise ValueError("the stacked form takes an (n, 2, F) tensor, got %s" % (tuple(a.shape),))
+        _check_attention(a[:, 0], a[:, 1], W1, b1, w2, mult)
+    else:
+        _check_attention(a, b, W1, b1, w2, mult)
+    return _AttentionFuse.apply(a, b, W1, b1, w2, mult)
+
+
 def pair_mlp_rank_list(X: torch.Tensor, C: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, w3: torch.Tensor,
                        b3: torch.Tensor, pair_query: torch.Tensor, pair_cand: torch.Tensor,
                        known_query: Optional[torch.Tensor] = None,
