@@ -39,16 +39,21 @@ class Attention(nn.Module):
     def forward(self, z):
         if self.fused and z.dim() == 3 and z.shape[1] == 2 and self._fusable(z[:, 0], z[:, 1]):
             return self._fused(z, None)
+        return self._chain(z)
+
+    def _chain(self, z):
         beta = self.dropout(torch.softmax(self.project(z), dim=1))
         return (beta * z).sum(1), beta
 
     def fuse(self, a, b):
         """``self.forward(torch.stack([a, b], 1))``; with ``fused`` set and fusable operands the two tables go to the
         kernel as they are, so the stack is never made.  Returns ``(out, beta)``, ``beta`` of shape ``(n, 2, 1)``; on
-        the fused route ``beta`` (the weights after dropout) carries no gradient."""
+        the fused route ``beta`` (the weights after dropout) carries no gradient.  Operands that are not fusable as
+        they are (rows off a 16-byte boundary, say) take the torch chain on their stack, not the kernel on a copy."""
         if self.fused and a.dim() == 2 and a.shape == b.shape and self._fusable(a, b):
             return self._fused(a, b)
-        return self.forward(torch.stack([a, b], dim=1))
+        z = torch.stack([a, b], dim=1)
+        return self._chain(z) if self.fused else self.forward(z)
 
     def _fusable(self, a, b):
         p = self.project

@@ -1556,10 +1556,16 @@ def attention_fuse(a: torch.Tensor, b: torch.Tensor, W1: torch.Tensor, b1: torch
     factors of the two weights; a constant).  ``b=None`` takes ``a`` as the stacked ``(n, 2, F)`` tensor.  ``out`` is
     ``(n, F)``, ``beta`` ``(n, 2)`` (after the multiplier) and NOT differentiable.  Differentiable once in ``a``, ``b``,
     ``W1``, ``b1``, ``w2``: the backward recomputes the hidden layer and the softmax, autograd keeps the inputs only, and
-    every sum is free of float atomics (bit-identical from run to run).  Nothing here synchronises."""
+    every sum is free of float atomics (bit-identical from run to run).  Nothing here synchronises.
+
+    Operand forms: a table that is column-strided, whose rows are no multiple of 4 floats apart or that starts off a
+    16-byte boundary is copied by the op (the stacked form then gets its gradient as one stacked copy); a non-contiguous
+    ``W1``, ``b1``, ``w2`` or ``mult`` (``lin.weight.t()`` of a transposed leaf, a column slice) is made contiguous here,
+    and its gradient reaches the leaf in the leaf's layout; the upstream gradient may have any strides."""
     _require_device(a, b, W1, b1, w2, mult)
     if mult is not None and not mult.is_contiguous():
         mult = mult.contiguous()
+    W1, b1, w2 = (t if t.is_contiguous() else t.contiguous() for t in (W1, b1, w2))
     if b is None:
         if a.dim() != 3 or a.shape[1] != 2:
             raise ValueError("the stacked form takes an (n, 2, F) tensor, got %s" % (tuple(a.shape),))

@@ -2,7 +2,8 @@
 
 ``reference`` is the contract, line by line.  ``exact_design`` makes operands on which fp32 is exact in ANY order of
 summation, so a kernel must EQUAL the restatement rounded to fp32; ``float_design`` draws operands the way the model
-meets them."""
+meets them, or with scaled weights that saturate ``tanh`` and the softmax; ``block_partials`` is what each block of rows
+adds to the three parameter sums; ``poison`` / ``classes`` / ``restate`` are the designs with one non-finite element."""
 import numpy as np
 
 HIDDEN = 16
@@ -127,13 +128,124 @@ def exact_bound(d):
     return float(max(sums)) if n else 0.0
 
 
-def float_design(n_rows, F, seed):
+def float_design(n_rows, F, seed, w1_scale=1, w2_scale=1):
     """``W1``, ``b1``, ``w2`` as ``nn.Linear`` initialises them (uniform in +-1 / sqrt(fan_in)), ``A ~ N(0, 1)``,
-    ``B ~ 0.5 N(0, 1)``, ``g ~ N(0, 1)``, ``M`` a ``p = 0.5`` dropout multiplier (0 or 2)."""
+    ``B ~ 0.5 N(0, 1)``, ``g ~ N(0, 1)``, ``M`` a ``p = 0.5`` dropout multiplier (0 or 2).  ``w1_scale`` multiplies
+    ``W1`` and ``b1`` and ``w2_scale`` multiplies ``w2`` (the same draws; 1 changes nothing): larger weights leave the
+    linear regime, so ``tanh`` and the softmax saturate and the backward's two cancellations carry the error."""
     rng = np.random.default_rng(seed)
     k1, k2 = 1.0 / np.sqrt(F), 1.0 / np.sqrt(HIDDEN)
     f32 = lambda t: np.ascontiguousarray(t, dtype=np.float32)
     return {"A": f32(rng.standard_normal((n_rows, F))), "B": f32(0.5 * rng.standard_normal((n_rows, F))),
-            "W1": f32(rng.uniform(-k1, k1, (HIDDEN, F))), "b1": f32(rng.uniform(-k1, k1, HIDDEN)),
-            "w2": f32(rng.uniform(-k2, k2, HIDDEN)), "M": f32(2.0 * (rng.random((n_rows, 2)) < 0.5)),
+            "W1": f32(w1_scale * rng.uniform(-k1, k1, (HIDDEN, F))), "b1": f32(w1_scale * rng.uniform(-k1, k1, HIDDEN)),
+            "w2": f32(w2_scale * rng.uniform(-k2, k2, HIDDEN)), "M": f32(2.0 * (rng.random((n_rows, 2)) < 0.5)),
             "g": f32(rng.standard_normal((n_rows, F)))}
+
+
+def regime(d):
+    """Where a float design sits, from the float64 restatement without the multiplier: the share of rows whose smaller
+    weight is below 1e-3, the share of hidden units with ``|h| > 0.99``, and the smallest weight rounded to fp32."""
+    z = np.stack([d["A"], d["B"]], 1).astype(np.float64)
+    h = np.tanh(z @ d["W1"].astype(np.float64).T + d["b1"].astype(np.float64))
+    beta = reference(d["A"], d["B"], d["W1"], d["b1"], d["w2"], None, d["g"])["beta"]
+    return float((beta.min(1) < 1e-3).mean()), float((np.abs(h) > 0.99).mean()), float(beta.astype(np.float32).min())
+
+
+BLOCK_ROWS = 64  # DGMI_ATTN_BLOCK_ROWS (test_attention_host.py holds it to the header)
+
+
+def block_partials(d):
+    """The restatement restricted to each block of ``BLOCK_ROWS`` rows, rounded to fp32: ``dW1`` (blocks, 16, F), ``db1``
+    and ``dw2`` (blocks, 16), what each block adds to the three parameter sums."""
+    n = d["A"].shape[0]
+    parts = {"dW1": [], "db1": [], "dw2": []}
+    for lo in range(0, n, BLOCK_ROWS):
+        rows = slice(lo, min(lo + BLOCK_ROWS, n))
+        r = reference(d["A"][rows], d["B"][rows], d["W1"], d["b1"], d["w2"], None if d["M"] is None else d["M"][rows], d["g"][rows])
+        for k in parts:
+            parts[k].append(r[k].astype(np.float32))
+    return {k: np.stack(v) for k, v in parts.items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# poisoned designs: one element of one operand replaced
+FINITE, NAN, POS_INF, NEG_INF = 0, 1, 2, 3
+
+
+def poison(d, operand, row, col, value):
+    """A copy of design ``d`` with ``d[operand][row, col] = value`` (``operand`` one of A, B, g, M)."""
+    e = dict(d)
+    e[operand] = d[operand].copy()
+    e[operand][row, col] = value
+    return e
+
+
+def classes(t):
+    """Per element: ``FINITE``, ``NAN``, ``POS_INF`` or ``NEG_INF`` (int8, the shape of ``t``)."""
+    t = np.asarray(t)
+    c = np.zeros(t.shape, dtype=np.int8)
+    c[np.isnan(t)] = NAN
+    c[np.isposinf(t)] = POS_INF
+    c[np.isneginf(t)] = NEG_INF
+    return c
+
+
+def restate(d, dtype=np.float64, reverse=False):
+    """``reference`` on design ``d`` carried out in ``dtype``, with the columns (the index of every sum over the width)
+    in reverse order when ``reverse`` is set: the same contract, other roundings and another order of summation."""
+    A, B, W1, b1, w2, g = (np.asarray(d[k], dtype=dtype) for k in ("A", "B", "W1", "b1", "w2", "g"))
+    if reverse:
+        A, B, W1, g = A[:, ::-1], B[:, ::-1], W1[:, ::-1], g[:, ::-1]
+    n = A.shape[0]
+    Mx = np.ones((n, 2), dtype=dtype) if d["M"] is None else np.asarray(d["M"], dtype=dtype)
+    one = dtype(1)
+    with np.errstate(all="ignore"):
+        z = np.stack([A, B], 1)
+        h = np.tanh(np.einsum("ncf,hf->nch", z, W1) + b1)
+        s = np.einsum("nch,h->nc", h, w2)
+        e = np.exp(s - s.max(1, keepdims=True))
+        beta = e / e.sum(1, keepdims=True)
+        bp = beta * Mx
+        out = bp[:, 0, None] * A + bp[:, 1, None] * B
+        db = Mx * np.einsum("nf,ncf->nc", g, z)
+        ds = beta * (db - (beta * db).sum(1, keepdims=True))
+        dpre = ds[:, :, None] * w2.reshape(1, 1, -1) * (one - h * h)
+        dz = bp[:, :, None] * g[:, None, :] + np.einsum("nch,hf->ncf", dpre, W1)
+        r = {"out": out, "beta": bp, "dA": dz[:, 0], "dB": dz[:, 1], "dW1": np.einsum("nch,ncf->hf", dpre, z),
+             "db1": dpre.sum((0, 1)), "dw2": np.einsum("nc,nch->h", ds, h)}
+    if reverse:
+        for k in ("out", "dA", "dB", "dW1"):
+            r[k] = r[k][:, ::-1]
+    return r
+
+
+POISON_SHAPE = (200, 132, 5)   # rows, width, seed of the unscaled float design: fourth block ragged, last j ragged
+POISON_ROWS = (0, 15, 16, 63, 64, 199)
+POISON_COLS = {"A": (0, 131), "B": (0, 131), "g": (0, 131), "M": (0, 1)}
+POISON_VALUES = {"A": (np.nan, np.inf, -np.inf, 3.0), "B": (np.nan, np.inf, -np.inf, 3.0), "g": (np.nan, np.inf, -np.inf, 3.0),
+                 "M": (np.nan, np.inf, -np.inf)}
+
+
+def poison_cases():
+    """``(operand, row, col, value)``: every listed row with every listed column for every operand, the values in turn."""
+    out = []
+    for operand in ("A", "B", "g", "M"):
+        values = POISON_VALUES[operand]
+        for ri, row in enumerate(POISON_ROWS):
+            for ci, col in enumerate(POISON_COLS[operand]):
+                out.append((operand, row, col, values[(2 * ri + ci) % len(values)]))
+    return out
+
+
+#: elements of a poisoned design's outputs whose class depends on rounding or on the order of summation (the three
+#: restatements of ``class_disagreements`` differ there): ``{(operand, row, col, repr(value)): {output: [index, ...]}}``.
+#: The host test holds this table to what it computes; the GPU test skips exactly these elements in its class check.
+POISON_LEFT_OUT = {}
+
+
+def class_disagreements(d):
+    """``{output: boolean mask}`` of the elements where the class map of the float64 restatement differs from that of the
+    fp32 restatement or from that of the float64 restatement with the columns reversed."""
+    base = restate(d)
+    others = (restate(d, np.float32), restate(d, np.float64, reverse=True))
+    return {k: np.logical_or.reduce([classes(o[k]) != classes(base[k]) for o in others]) for k in OUTPUTS}

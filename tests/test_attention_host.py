@@ -2,7 +2,9 @@
 exports them and ``ATTN_SIGNATURES`` matches type for type; argument validation and workspace sizing return codes before
 any launch; the ops are registered for the device only; the module flag is opt-in and falls back to the chain on CPU
 tensors; the float64 restatement agrees with float64 autograd of the module's expression; the exact designs keep their
-margins, classes and bound."""
+margins, classes and bound; and what ``test_gpu_attention_forms.py`` relies on: every block of its exact designs adds to
+all three parameter sums (the first suite's width shapes do not), the scaled float design saturates, and the poisoned
+designs have one class map in any precision and order of summation."""
 import ctypes
 import os
 import re
@@ -262,3 +264,110 @@ def test_exact_designs_keep_their_margins_classes_and_bound(n_rows, F, mult):
         if mult:
             assert np.any((d["M"] == 0).all(1))
             assert np.any(r32["dA"][(d["M"] == 0).all(1)] == 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the designs of test_gpu_attention_forms.py do what that file relies on
+FORMS_WIDTHS = (4, 12, 20, 28, 32, 36, 124, 132, 252, 260, 508, 512)
+FORMS_PART_COUNTS = (15, 16, 17, 240, 241, 255, 256, 257, 1023)
+
+
+def _forms_exact_cases():
+    R, G = K.BLOCK_ROWS, _constant("DGMI_ATTN_MAX_WORKGROUPS")
+    return ([(200, F) for F in FORMS_WIDTHS] + [(R * G + 2 * R + 3, 32), (R * G + 2 * R + 3, 260)]
+            + [(R * k - 3, 16) for k in FORMS_PART_COUNTS])
+
+
+def _every_block_contributes(d):
+    p = K.block_partials(d)
+    assert all(v.dtype == np.float32 and v.shape[0] == -(-d["A"].shape[0] // K.BLOCK_ROWS) for v in p.values())
+    return {k: bool(np.all(np.any(v.reshape(v.shape[0], -1) != 0, axis=1))) for k, v in p.items()}
+
+
+def test_block_rows_mirror_the_header():
+    assert K.BLOCK_ROWS == _constant("DGMI_ATTN_BLOCK_ROWS")
+
+
+@pytest.mark.parametrize("mult", [False, True])
+@pytest.mark.parametrize("n_rows,F", _forms_exact_cases())
+def test_every_block_of_the_forms_designs_adds_to_all_three_sums(n_rows, F, mult):
+    """The width and partial-count cases of the forms file: fp32 is exact in any order, and EVERY block's partial of
+    dW1, db1 and dw2 is non-zero after rounding, so a sum carried across blocks or across partials is a sum of non-zero
+    terms.  The partials add up to the restatement's sums."""
+    d = K.exact_design(n_rows, F, mult)
+    assert 8 * K.exact_bound(d) < 2 ** 24
+    assert _every_block_contributes(d) == {"dW1": True, "db1": True, "dw2": True}
+    p = K.block_partials(d)
+    r = K.reference(d["A"], d["B"], d["W1"], d["b1"], d["w2"], d["M"], d["g"])
+    for k in p:
+        assert np.array_equal(p[k].astype(np.float64).sum(0).astype(np.float32), r[k].astype(np.float32)), k
+
+
+@pytest.mark.parametrize("mult", [False, True])
+@pytest.mark.parametrize("n_rows,F", [(65, 16), (65, 128), (65, 512), (65537, 128)])
+def test_the_first_suites_width_shapes_carry_no_second_partial(n_rows, F, mult):
+    """Why the forms file has shapes of its own: at R + 1 and R G + 1 rows the lone row of the last block is of class 1
+    (saturated softmax, ds = 0), so that block's partial of all three sums is exactly zero."""
+    p = K.block_partials(K.exact_design(n_rows, F, mult))
+    for k, v in p.items():
+        assert not v[-1].any() and v[0].any(), k
+
+
+def test_scaled_float_design_keeps_the_default_and_reaches_saturation():
+    for shape in ((763, 128, 40), (1256, 256, 41)):
+        plain, one = K.float_design(*shape), K.float_design(*shape, w1_scale=1, w2_scale=1)
+        assert all(np.array_equal(plain[k], one[k]) and plain[k].dtype == np.float32 for k in plain)
+        small, sat, least = K.regime(plain)
+        assert small == 0.0 and sat < 1e-3 and least > 0.2                    # the linear regime of the first suite
+        d = K.float_design(*shape, w1_scale=4, w2_scale=8)
+        for k in ("A", "B", "g", "M"):
+            assert np.array_equal(d[k], plain[k]), k
+        assert np.array_equal(d["W1"], (4 * plain["W1"].astype(np.float64)).astype(np.float32))
+        small, sat, least = K.regime(d)
+        print("float_design%s x (4, 8): weight < 1e-3 in %.1f %% of rows, |h| > 0.99 in %.1f %% of units, least fp32 weight %.3g"
+              % (shape, 100 * small, 100 * sat, least))
+        assert small >= 0.15 and sat >= 0.10 and least > 0.0
+
+
+def test_poison_and_classes():
+    d = K.float_design(5, 8, 0)
+    e = K.poison(d, "B", 3, 7, -np.inf)
+    assert e["B"][3, 7] == -np.inf and np.isfinite(d["B"]).all() and e["A"] is d["A"] and e["B"] is not d["B"]
+    c = K.classes(np.array([[1.0, np.nan], [np.inf, -np.inf]], dtype=np.float32))
+    assert c.tolist() == [[K.FINITE, K.NAN], [K.POS_INF, K.NEG_INF]]
+    cases = K.poison_cases()
+    for operand in ("A", "B", "g", "M"):
+        mine = [c for c in cases if c[0] == operand]
+        assert {(c[1], c[2]) for c in mine} == {(r, col) for r in K.POISON_ROWS for col in K.POISON_COLS[operand]}
+        assert {repr(c[3]) for c in mine} == {repr(v) for v in K.POISON_VALUES[operand]}
+
+
+def test_poisoned_designs_have_one_class_map_in_any_precision_and_order():
+    """For every poisoned design of the forms file: NaN / +Inf / -Inf / finite per element of the float64 restatement is
+    also what the restatement gives in fp32 and with the columns reversed, except at the elements ``POISON_LEFT_OUT``
+    names (at most 1 % of an output); the poisoned row is not finite unless the value is, and the restatement keeps a
+    poisoned row out of every other row."""
+    d0 = K.float_design(*K.POISON_SHAPE)
+    assert K.regime(d0)[2] > 0.2                                                 # no weight underflows on this design
+    clean = K.restate(d0)
+    named = {}
+    for case in K.poison_cases():
+        operand, row, col, value = case
+        d = K.poison(d0, *case)
+        diff = K.class_disagreements(d)
+        where = {k: [tuple(int(i) for i in idx) for idx in np.argwhere(v)] for k, v in diff.items() if v.any()}
+        if where:
+            named[(operand, row, col, repr(value))] = where
+        for k, v in diff.items():
+            assert v.sum() <= 0.01 * v.size, (case, k)
+        r = K.restate(d)
+        other = np.arange(d0["A"].shape[0]) != row
+        for k in ("out", "beta", "dA", "dB"):
+            assert np.array_equal(r[k][other], clean[k][other]), (case, k)
+        if operand == "g":
+            assert np.array_equal(r["out"], clean["out"]) and np.array_equal(r["beta"], clean["beta"])
+        if not np.isfinite(value):
+            assert not np.isfinite(r["dA"][row]).all() and not np.isfinite(r["dW1"]).all(), case
+        else:
+            assert all(np.isfinite(r[k]).all() for k in K.OUTPUTS), case
+    assert named == K.POISON_LEFT_OUT
