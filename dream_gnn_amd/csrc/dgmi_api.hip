@@ -347,7 +347,7 @@ static int spmm_sliced(const int32_t* segptr, const int32_t* indices, const floa
   dgmi::SlicedArgs a{segptr, indices, vals, X, x_bytes, ldx, src_scale, dst_scale, Y, ldy, n_dst, n_src, F, n_slices,
                      static_cast<float*>(planes), F, sliced_chunk_rows(n_dst, n_slices, F), eid, keep, n_keep,
                      {act, act_slope, out_mask, ld_mask, out_mask_scale}, column_passes == 1, id_multiplicity == 1};
-  return from_hip(x_bytes == 4 ? dgmi::spmm_sliced_f32(a, as_stream(stream)) : dgmi::spmm_sliced_bf16(a, as_stream(stream)));
+  return from_hip(dgmi::spmm_sliced(a, as_stream(stream)));
 }
 
 DGMI_API int dgmi_spmm_sliced_f32(const int32_t* segptr, const int32_t* indices, const float* vals,

@@ -115,8 +115,8 @@ hipError_t radix_sort_records(const int32_t* key, const int32_t* eid_in, const i
                               int32_t n_rows, int32_t n_cols, int32_t* keys_out, int32_t* eid_out, int32_t* col_out, int32_t* flag,
                               void* workspace, hipStream_t s);
 
-// Source-sliced CSR (dgmi_csr.hip) and the XCD-local SpMM over it (dgmi_sliced.hip, dgmi_sliced_bf16.hip; what the two
-// share: dgmi_sliced_common.h).
+// Source-sliced CSR (dgmi_csr.hip) and the XCD-local SpMM over it (dgmi_sliced.hip; its one gather body:
+// dgmi_sliced_kernel.h; the bf16 copy of a table: dgmi_sliced_bf16.hip).
 hipError_t csr_sliced_from_coo_i32(const int32_t* row, const int32_t* col, int64_t E, int64_t n_rows,
                                    int64_t n_cols, int64_t n_slices, int64_t slice_width,
                                    int32_t* segptr, int32_t* indices, int32_t* eid, void* workspace,
@@ -139,7 +139,7 @@ struct SlicedArgs {
   const int32_t* indices;
   const float* vals;       // nullable, sliced order
   const void* X;           // the gathered table: fp32, or bf16 bit patterns
-  int x_bytes;             // bytes per element of X: 4 (spmm_sliced_f32) or 2 (spmm_sliced_bf16)
+  int x_bytes;             // bytes per element of X: 4 (fp32) or 2 (bf16)
   int64_t ldx;             // in elements; a multiple of 16 / x_bytes, as F is
   const float* src_scale;  // nullable; must be null for a bf16 table (the scale belongs to rows_to_bf16)
   const float* dst_scale;  // nullable
@@ -162,13 +162,12 @@ struct SlicedArgs {
 // *fail = 1 when some row has no such form (dgmi_edge.hip); mult[p] = m - 1
 hipError_t row_multiplicity_f32(const int32_t* indptr, const float* vals, int64_t n_rows, float rel_tol, float* row_scale,
                                 int32_t* mult, int32_t* fail, hipStream_t s);
-hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s);
+// x_bytes == 4: an fp32 table.  x_bytes == 2: the same product gathering from a bf16 table — F and ldx multiples of 8, no
+// source scale (an error).  Planes, dst_scale, Y: fp32 either way (dgmi_sliced.hip).
+hipError_t spmm_sliced(const SlicedArgs& a, hipStream_t s);
 // the slice count of the layout a plain fp32 product of this shape should be given (dgmi_owned.hip; include/dgmi_layout.h)
 int sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, bool id_mult);
 
-// The same product gathering from a bf16 table (dgmi_sliced_bf16.hip): x_bytes == 2, F and ldx multiples of 8, no source
-// scale (an error).  Planes, dst_scale, Y: fp32.
-hipError_t spmm_sliced_bf16(const SlicedArgs& a, hipStream_t s);
 // out[r, :] = bf16_rne(scale[r] * X[r, :]) (scale nullable), one streaming pass; F, ldo multiples of 8, ldx of 4
 hipError_t rows_to_bf16(const float* X, int64_t ldx, const float* scale, int64_t n, int64_t F, uint16_t* out, int64_t ldo,
                         hipStream_t s);

@@ -55,40 +55,12 @@ namespace {
 constexpr int kOwnedTouchChunk = 4;  // tasks the toucher touches for at a time
 constexpr int kOwnedTouchLead = 8;   // tasks between the counter and the first task of the chunk it touches for
 
-// An fp32 table: a lane owns 4 columns — one 16-B load, one float4 sum, one float4 of the LPR slots of an LDS row.
-struct OwnedRowF32 {
-  typedef float Elem;
-  typedef float4 Reg;  // a gathered row: this lane's columns
-  typedef float4 Acc;
-  static constexpr int kCols = 4;
+// An fp32 table (columns, load, sums and the canonical step: RowF32, dgmi_sliced_common.h): one float4 of the LPR
+// slots of an LDS row.
+struct OwnedRowF32 : RowF32 {
   static constexpr int kLaneSlots = 1;  // float4 LDS slots per lane and row
-  static constexpr int kMaxLpr = 64;    // the widest lane group: 256 columns either way
   static constexpr bool kCarry = true;  // the hand-over may be built (measured: profiles/owned_carry/README.md)
   static constexpr bool kPeel = true;   // groups 0 and 1 of a run stand in front of the group loop (owned_body)
-
-  static __device__ __forceinline__ Acc zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-  template <bool OFF32>
-  static __device__ __forceinline__ Reg load(const Elem* __restrict__ X, const Elem* __restrict__ Xc, int idx, int64_t ldx,
-                                             uint32_t row_bytes, uint32_t col_bytes) {
-    return ld_row<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
-  }
-
-  // acc + x / fmaf(m, x, acc): the canonical step
-  template <bool MULT>
-  static __device__ __forceinline__ void add(Acc& acc, float m, const Reg& x) {
-    if (MULT) {
-      acc.x = fmaf(m, x.x, acc.x);
-      acc.y = fmaf(m, x.y, acc.y);
-      acc.z = fmaf(m, x.z, acc.z);
-      acc.w = fmaf(m, x.w, acc.w);
-    } else {
-      acc.x += x.x;
-      acc.y += x.y;
-      acc.z += x.z;
-      acc.w += x.w;
-    }
-  }
 
   // the segment sum joins the running sum in this lane's slot of the row (`first`: slice 0 starts it).  (LPR goes
   // unused here and in sum: the body calls both policies alike, and the bf16 one's second half lies LPR slots further.)
@@ -124,56 +96,18 @@ struct OwnedRowF32 {
   }
 };
 
-// A bf16 table: a lane owns 8 columns — one 16-B load (ld_row8), each of its four dwords widened by a shift and a mask
-// into the two floats of one column PAIR, as spmm_sliced_bf16_kernel does (dgmi_sliced_bf16.hip).  The eight sums are
-// kept as those four pairs, in two-element vectors: the adds are packed adds (or packed fmas) of a widened dword onto
-// its pair, element for element what acc + x / fmaf(m, x, acc) give.  Left as eight scalars the compiler chooses the
-// pairs of its packed adds itself, not always these, and moves the sums between them once per group of the window
-// (profiles/owned_one_body/README.md).  An LDS row of one column round is 2 LPR slots, planar: the float4 of columns
-// 0..3 of all LPR lanes first, then the float4 of columns 4..7 of all lanes — each of a lane's two 16-byte accesses is
-// contiguous across its lane group (a 32-byte lane stride would make every access a two-way bank conflict).  The plan:
-// owned_plan with cols_per_lane = 8.
-struct OwnedRowBf16 {
-  typedef uint16_t Elem;
-  typedef v4u Reg;
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  struct Acc {
-    v2f p[4];  // columns (0, 1), (2, 3), (4, 5), (6, 7)
-  };
-  static constexpr int kCols = 8;
+// A bf16 table (columns, load, the sums as four column pairs and the canonical step: RowBf16, dgmi_sliced_common.h —
+// the pair's gather, spmm_sliced_bf16_kernel, sums with the same members).  An LDS row of one column round is 2 LPR
+// slots, planar: the float4 of columns 0..3 of all LPR lanes first, then the float4 of columns 4..7 of all lanes — each
+// of a lane's two 16-byte accesses is contiguous across its lane group (a 32-byte lane stride would make every access a
+// two-way bank conflict).  The plan: owned_plan with cols_per_lane = 8.
+struct OwnedRowBf16 : RowBf16 {
   static constexpr int kLaneSlots = 2;
-  static constexpr int kMaxLpr = 32;
   static constexpr bool kCarry = false;  // the hand-over has not been measured on a bf16 table
   // One plain group loop.  With groups 0 and 1 in front of it, as the fp32 kernels have them, the products take the
   // same time, but all twelve kernels need 82-84 VGPRs instead of 72-80 and the compiler states 5 waves per SIMD where
   // the separate bf16 kernel stated 6 (profiles/owned_one_body/README.md).
   static constexpr bool kPeel = false;
-
-  static __device__ __forceinline__ Acc zero() { return Acc{{v2f(0.f), v2f(0.f), v2f(0.f), v2f(0.f)}}; }
-  static __device__ __forceinline__ Acc pairs(const float4& a, const float4& b) {
-    return Acc{{v2f{a.x, a.y}, v2f{a.z, a.w}, v2f{b.x, b.y}, v2f{b.z, b.w}}};
-  }
-  static __device__ __forceinline__ float4 half(const Acc& t, int h) {  // columns 4 h .. 4 h + 3
-    return make_float4(t.p[2 * h].x, t.p[2 * h].y, t.p[2 * h + 1].x, t.p[2 * h + 1].y);
-  }
-
-  template <bool OFF32>
-  static __device__ __forceinline__ Reg load(const Elem* __restrict__ X, const Elem* __restrict__ Xc, int idx, int64_t ldx,
-                                             uint32_t row_bytes, uint32_t col_bytes) {
-    return ld_row8<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
-  }
-
-  template <bool MULT>
-  static __device__ __forceinline__ void add(Acc& acc, float m, const Reg& x) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {  // bf16 -> fp32 is a shift (element 2k) or a mask (element 2k + 1): exact (widen)
-      const v2f w = {__uint_as_float(x[k] << 16), __uint_as_float(x[k] & 0xffff0000u)};
-      if (MULT)
-        acc.p[k] = __builtin_elementwise_fma(v2f(m), w, acc.p[k]);
-      else
-        acc.p[k] += w;
-    }
-  }
 
   template <int LPR>
   static __device__ __forceinline__ Acc sum(const float4* slot) {

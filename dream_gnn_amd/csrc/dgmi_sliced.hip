@@ -12,40 +12,21 @@
 // a second, streaming kernel adds the 8 planes in slice order (deterministic) and applies
 // dst_scale.  Extra traffic: 2 * 8 * N_dst * 4F bytes of plane write + read, against
 // nnz * 4F bytes of gather that now come out of L2.
+//
+// The gathered table is fp32 or a bf16 copy of it (rows_to_bf16, dgmi_sliced_bf16.hip): a row of 2F bytes, the slice of
+// a 100 000-source table at F = 128 3.2 MB — it fits an XCD's 4 MiB L2 at full width.  Products, sums, planes and Y are
+// fp32 either way.  Both gather kernels are ONE body (sliced_body, dgmi_sliced_kernel.h: the canonical sum, the grid,
+// KEEP and VALS are described there) under a row policy each, launched through one table of instantiations; the result
+// from a bf16 table is bit-identical to the fp32 product of the upcast table, whatever the launch geometry of either.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dgmi_sliced_common.h"
+#include "dgmi_sliced_kernel.h"
 
 namespace dgmi {
 namespace {
 
-// A (row, slice) segment is short (deg / n_slices: 12-25 edges at config 4).  In the slice-major
-// layout the segments of consecutive rows of one slice are contiguous, so each LPR-lane *group*
-// of the wave (F=128: a half-wave) streams the edges of kRowsPerGroup consecutive rows as ONE
-// run — ids read LPR at a time by the group's own lanes, one gathered source row per group per
-// wave-instruction, 8 gathers in flight per group — and cuts the running sum at the row
-// boundaries (held one per lane, fetched with ds_bpermute when crossed).  No bubble between
-// rows, no cross-group reduction.
-//
-// The sum of a (row, slice) segment is CANONICAL: acc starts at +0 and takes the segment's edges in layout order,
-// acc = acc + x_p (unit values) or acc = fmaf(w_p, x_p, acc) (w_p: the edge's factors multiplied in the order below),
-// whether a batch of 8 lies inside one row (no boundary tests) or crosses a boundary (per-edge tests).  With the planes
-// added in slice order, a product is a function of the layout and the operands alone: not of the rows per lane group,
-// the lane-group width, the row chunks, the column passes, the tapered tail, the touchers or — for a table of bf16 values
-// — of the table's element width (dgmi_sliced_bf16.hip computes the same).
-//
-// grid.x = n_slices * (worker blocks + toucher blocks); the rows of a worker block's lane groups: sliced_run
-// (dgmi_sliced_common.h).  block b: slice = b % n_slices.
-// Rows [row_begin, row_end) of every slice; plane row index is relative to row_begin.
-// KEEP: edge dropout on the fly — an edge whose keep(eid[p]) fails (dgmi_keep.h) is flagged in the sign
-// bit of its source id; its gather repeats the group's previous row (an L1 hit — never one fixed row,
-// which would turn 10 % of all gathers into traffic on a single L2 channel) and its contribution is
-// replaced by zeros.
-// VALS: 0 = unit edge values; 1 = vals[p]; 2 = small integer multiplicities carried in the id words themselves (bits
-// kMultShift..30 hold m - 1): the reference's adjacencies are D^-1 (A + A^T + I) (data_loader.py:297-308, utils.py:11-17),
-// i.e. value = row scale x multiplicity — the scale goes where dst_scale / src_scale go, the multiplicity rides with the
-// id: no value stream (4 B / edge), no second cross-lane hand-off per edge.
+// An fp32 table: a lane owns 4 columns.
 template <int LPR, int VALS, bool HAS_SS, bool KEEP, bool OFF32>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel(
     const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices,
@@ -53,137 +34,20 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void spmm_sliced_vec4_kernel
     const float* __restrict__ src_scale, float* __restrict__ planes, int64_t ldp, int64_t n_dst,
     int64_t row_begin, int64_t row_end, int F, int n_slices, const int32_t* __restrict__ eid,
     const KeepSeg* __restrict__ keep, int n_keep, int touch_lead, SlicedRuns runs, int touch_group) {
-  constexpr int G = kWave / LPR;
-  constexpr bool HAS_VALS = VALS == 1;
-  constexpr bool MULT = VALS == 2;
-  constexpr bool WEIGHTED = HAS_VALS || HAS_SS || MULT;  // a per-edge factor exists
-  constexpr bool W_LANE = HAS_VALS || HAS_SS;            // ... and travels in a register of its own
-  constexpr int kIdMask = MULT ? (int)kMultIdMask : 0x7fffffff;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x >> 6;
-  const int grp = lane / LPR, glane = lane % LPR, gbase = grp * LPR;
-  const int slice = (int)(blockIdx.x % (unsigned)n_slices);
-  int64_t block = blockIdx.x / (unsigned)n_slices;
-  if (touch_group > 0 &&
-      touch_ahead<HAS_VALS, KEEP>(segptr, indices, vals, eid, n_dst, row_begin, row_end, slice, runs, touch_lead, touch_group,
-                                  lane, wave, block))
-    return;
-  const SlicedRun run = sliced_run(runs, block, wave * G + grp);
-  const int nr = run.rows;  // < LPR: a group's row boundaries live one per lane
-  if (nr == 0) return;  // whole group idle (lanes of other groups carry on)
-  const int64_t row0 = row_begin + run.first;
-  int col = ((int)blockIdx.y * LPR + glane) * 4;
-  const bool col_ok = col < F;
-  if (!col_ok) col = 0;
-  const float* Xc = X + col;
-  const uint32_t row_bytes = (uint32_t)ldx * 4u, col_bytes = (uint32_t)col * 4u;
-  const int32_t* sp = segptr + (int64_t)slice * n_dst + row0;
-  float* prow = planes + ((int64_t)slice * (row_end - row_begin) + (row0 - row_begin)) * ldp + col;
+  sliced_body<SlicedRowF32, LPR, VALS, HAS_SS, KEEP, OFF32>(segptr, indices, vals, X, ldx, src_scale, planes, ldp, n_dst, row_begin,
+                                                            row_end, F, n_slices, eid, keep, n_keep, touch_lead, runs, touch_group);
+}
 
-  const KeepPre first = first_seg<KEEP>(keep, n_keep);
-  const int my_b = sp[glane < nr ? glane : nr];  // lane k holds boundary k (k <= nr)
-  const int e_begin = __shfl(my_b, gbase, kWave);
-  const int e_end = __shfl(my_b, gbase + nr, kWave);
-  int r = 0;
-  int next_b = __shfl(my_b, gbase + 1, kWave);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  // ids (and weights) one batch ahead of the gathers that use them
-  int nxt_idx = 0;
-  float nxt_w = 0.f;
-  int last_row = -1;  // KEEP: the row this group gathered last (where a dropped edge's load is parked)
-  if (e_begin < e_end) {
-    const int q = e_begin + glane < e_end ? e_begin + glane : e_begin;
-    nxt_idx = fetch_id<KEEP>(indices, eid, first, keep, n_keep, q);
-    if (W_LANE) {
-      nxt_w = HAS_VALS ? vals[q] : 1.f;
-      if (HAS_SS) nxt_w *= src_scale[(KEEP || MULT) ? nxt_idx & kIdMask : nxt_idx];
-    }
-  }
-  for (int base = e_begin; base < e_end; base += LPR) {
-    const int n = min(LPR, e_end - base);
-    const int my_idx = nxt_idx;
-    const float my_w = nxt_w;
-    if (base + LPR < e_end) {
-      const int nb = base + LPR;
-      const int q = nb + glane < e_end ? nb + glane : nb;
-      nxt_idx = fetch_id<KEEP>(indices, eid, first, keep, n_keep, q);
-      if (W_LANE) {
-        nxt_w = HAS_VALS ? vals[q] : 1.f;
-        if (HAS_SS) nxt_w *= src_scale[(KEEP || MULT) ? nxt_idx & kIdMask : nxt_idx];
-      }
-    }
-    for (int j = 0; j < n; j += kUnroll) {
-      float4 v[kUnroll];
-      float w[kUnroll];
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int e = j + u;  // < LPR
-        int idx = __shfl(my_idx, gbase + e, kWave);
-        if (W_LANE) w[u] = __shfl(my_w, gbase + e, kWave);
-        if (MULT) {  // the multiplicity arrived with the id
-          const float m = (float)(((idx >> kMultShift) & kMultMax) + 1);
-          w[u] = W_LANE ? w[u] * m : m;
-        }
-        const bool dropped = KEEP && idx < 0;
-        if (KEEP) {
-          idx = dropped && last_row >= 0 ? last_row : idx & kIdMask;
-          last_row = idx;
-        } else if (MULT) {
-          idx &= kIdMask;
-        }
-        v[u] = ld_row<OFF32>(X, Xc, idx, ldx, row_bytes, col_bytes);
-        if (dropped) v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      // fast path (group-uniform): all 8 edges belong to the current row -> no per-edge boundary tests; the same
-      // in-order sum as below (the four columns are the ILP) (a timing-only build that took it for EVERY batch gained
-      // 2-7 %: the slow path is not what holds the kernel at 0.81 of the gather probe —
-      // profiles/r03_swept_experiment/README.md)
-      if (base + j + kUnroll <= next_b) {
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-          if (WEIGHTED) {
-            acc.x = fmaf(w[u], v[u].x, acc.x);
-            acc.y = fmaf(w[u], v[u].y, acc.y);
-            acc.z = fmaf(w[u], v[u].z, acc.z);
-            acc.w = fmaf(w[u], v[u].w, acc.w);
-          } else {
-            acc.x += v[u].x;
-            acc.y += v[u].y;
-            acc.z += v[u].z;
-            acc.w += v[u].w;
-          }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int u = 0; u < kUnroll; ++u) {
-        const int p = base + j + u;
-        if (p < e_end) {  // group-uniform
-          while (p >= next_b) {  // row(s) ended before this edge: emit them (empty rows emit zeros)
-            if (col_ok) store_plane_row(prow + (int64_t)r * ldp, acc);
-            acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            ++r;
-            next_b = __shfl(my_b, gbase + r + 1, kWave);
-          }
-          if (WEIGHTED) {
-            acc.x = fmaf(w[u], v[u].x, acc.x);
-            acc.y = fmaf(w[u], v[u].y, acc.y);
-            acc.z = fmaf(w[u], v[u].z, acc.z);
-            acc.w = fmaf(w[u], v[u].w, acc.w);
-          } else {
-            acc.x += v[u].x;
-            acc.y += v[u].y;
-            acc.z += v[u].z;
-            acc.w += v[u].w;
-          }
-        }
-      }
-    }
-  }
-  for (; r < nr; ++r) {  // the last non-empty row, then any trailing empty rows
-    if (col_ok) store_plane_row(prow + (int64_t)r * ldp, acc);
-    acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+// A bf16 table: a lane owns 8 columns.  Built for five waves per SIMD (96 VGPRs) like the fp32 kernel's forms without a
+// source scale; a per-edge weight together with dropout on the fly or with 8-lane groups needs more: four waves, no scratch.
+template <int LPR, int VALS, bool KEEP, bool OFF32>
+__global__ __launch_bounds__(kWave* kWavesPerBlock, (VALS != 0 && (KEEP || LPR == 8)) ? 4 : 5) void spmm_sliced_bf16_kernel(
+    const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ vals,
+    const uint16_t* __restrict__ X, int64_t ldx, float* __restrict__ planes, int64_t ldp, int64_t n_dst, int64_t row_begin,
+    int64_t row_end, int F, int n_slices, const int32_t* __restrict__ eid, const KeepSeg* __restrict__ keep, int n_keep,
+    int touch_lead, SlicedRuns runs, int touch_group) {
+  sliced_body<SlicedRowBf16, LPR, VALS, false, KEEP, OFF32>(segptr, indices, vals, X, ldx, nullptr, planes, ldp, n_dst, row_begin,
+                                                            row_end, F, n_slices, eid, keep, n_keep, touch_lead, runs, touch_group);
 }
 
 // Y[row] = dst_scale[row] * (plane_0[row] + plane_1[row] + ...) in slice order; one float4 per
@@ -265,51 +129,61 @@ hipError_t reduce_planes(const float* planes, int64_t ldp, int64_t rows, int64_t
   return hipGetLastError();
 }
 
-template <int LPR>
-hipError_t launch_sliced(const SlicedArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
-  const SlicedGeometry g = sliced_geometry(row_begin, row_end, a.F, a.n_src, a.ldx, a.n_slices, LPR, a.x_bytes);
-  dim3 block(kWave * kWavesPerBlock);
-  const int key = (a.vals ? 4 : (a.id_mult ? 8 : 0)) | (a.src_scale ? 2 : 0) | (a.n_keep > 0 ? 1 : 0);
-#define DGMI_LAUNCH_O(V, S, K, O)                                                                                      \
-  hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, V, S, K, O>), g.grid, block, 0, s, a.segptr, a.indices, a.vals,      \
-                     static_cast<const float*>(a.X), a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end, \
-                     (int)a.F, (int)a.n_slices, a.eid, static_cast<const KeepSeg*>(a.keep), a.n_keep, g.touch_lead, g.runs, \
-                     g.touch_group)
-#define DGMI_LAUNCH(V, S, K)                                              \
-  do {                                                                    \
-    if (g.off32) DGMI_LAUNCH_O(V, S, K, true); else DGMI_LAUNCH_O(V, S, K, false); \
-  } while (0)
-  switch (key) {
-    case 0: DGMI_LAUNCH(0, false, false); break;
-    case 1: DGMI_LAUNCH(0, false, true); break;
-    case 2: DGMI_LAUNCH(0, true, false); break;
-    case 3: DGMI_LAUNCH(0, true, true); break;
-    case 4: DGMI_LAUNCH(1, false, false); break;
-    case 5: DGMI_LAUNCH(1, false, true); break;
-    case 6: DGMI_LAUNCH(1, true, false); break;
-    case 7: DGMI_LAUNCH(1, true, true); break;
-    case 8: DGMI_LAUNCH(2, false, false); break;
-    case 9: DGMI_LAUNCH(2, false, true); break;
-    case 10: DGMI_LAUNCH(2, true, false); break;
-    default: DGMI_LAUNCH(2, true, true); break;
+// One instantiation: the kernel of the table's element type in this form.  A bf16 table has no source-scale form
+// (spmm_sliced refuses the request).
+template <typename Row, int LPR, int VALS, bool HAS_SS, bool KEEP, bool OFF32>
+void launch_form(const SlicedArgs& a, const SlicedGeometry& g, int64_t row_begin, int64_t row_end, hipStream_t s) {
+  const dim3 block(kWave * kWavesPerBlock);
+  const auto* X = static_cast<const typename Row::Elem*>(a.X);
+  const auto* keep = static_cast<const KeepSeg*>(a.keep);
+  if constexpr (!Row::kSrcScale) {
+    if constexpr (!HAS_SS)
+      hipLaunchKernelGGL((spmm_sliced_bf16_kernel<LPR, VALS, KEEP, OFF32>), g.grid, block, 0, s, a.segptr, a.indices, a.vals, X,
+                         a.ldx, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices, a.eid, keep, a.n_keep,
+                         g.touch_lead, g.runs, g.touch_group);
+  } else {
+    hipLaunchKernelGGL((spmm_sliced_vec4_kernel<LPR, VALS, HAS_SS, KEEP, OFF32>), g.grid, block, 0, s, a.segptr, a.indices,
+                       a.vals, X, a.ldx, a.src_scale, a.planes, a.ldp, a.n_dst, row_begin, row_end, (int)a.F, (int)a.n_slices,
+                       a.eid, keep, a.n_keep, g.touch_lead, g.runs, g.touch_group);
   }
-#undef DGMI_LAUNCH
-#undef DGMI_LAUNCH_O
+}
+
+// The gather launch of one row chunk [row_begin, row_end) at lane-group width LPR: the table of instantiations, VALS
+// (0 unit values, 1 a.vals, 2 a.id_mult) x source scale x dropout on the fly x 32-bit offsets.
+template <typename Row, int LPR>
+hipError_t launch_sliced(const SlicedArgs& a, int64_t row_begin, int64_t row_end, hipStream_t s) {
+  typedef void (*Form)(const SlicedArgs&, const SlicedGeometry&, int64_t, int64_t, hipStream_t);
+#define DGMI_FORMS(V, S) \
+  {{launch_form<Row, LPR, V, S, false, false>, launch_form<Row, LPR, V, S, false, true>}, \
+   {launch_form<Row, LPR, V, S, true, false>, launch_form<Row, LPR, V, S, true, true>}}
+  static constexpr Form table[3][2][2][2] = {{DGMI_FORMS(0, false), DGMI_FORMS(0, true)},
+                                             {DGMI_FORMS(1, false), DGMI_FORMS(1, true)},
+                                             {DGMI_FORMS(2, false), DGMI_FORMS(2, true)}};
+#undef DGMI_FORMS
+  const SlicedGeometry g = sliced_geometry(row_begin, row_end, a.F, a.n_src, a.ldx, a.n_slices, LPR, a.x_bytes);
+  table[a.vals ? 1 : (a.id_mult ? 2 : 0)][a.src_scale != nullptr][a.n_keep > 0][g.off32](a, g, row_begin, row_end, s);
   return hipGetLastError();
 }
 
-hipError_t launch_gather_f32(const SlicedArgs& a, int lpr, int64_t r0, int64_t r1, hipStream_t s) {
+// The lane-group widths a table's element type has: 8 .. 64 of an fp32 table, 8 .. 32 of a bf16 one (sliced_lpr).
+template <typename Row>
+hipError_t launch_gather(const SlicedArgs& a, int lpr, int64_t r0, int64_t r1, hipStream_t s) {
   switch (lpr) {
-    case 8: return launch_sliced<8>(a, r0, r1, s);
-    case 16: return launch_sliced<16>(a, r0, r1, s);
-    case 32: return launch_sliced<32>(a, r0, r1, s);
-    default: return launch_sliced<64>(a, r0, r1, s);
+    case 8: return launch_sliced<Row, 8>(a, r0, r1, s);
+    case 16: return launch_sliced<Row, 16>(a, r0, r1, s);
+    case 32: return launch_sliced<Row, 32>(a, r0, r1, s);
+    default:
+      if constexpr (Row::kMaxLpr >= 64)
+        return launch_sliced<Row, 64>(a, r0, r1, s);
+      else
+        return launch_sliced<Row, 32>(a, r0, r1, s);
   }
 }
 
-}  // namespace
-
-hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStream_t s) {
+// The chunk driver: cuts [0, n_dst) into row chunks; per chunk picks the lane-group width (sliced_lpr), runs the gather
+// and then the plane reduce with the chunk's dst_scale / Y / mask offsets.
+template <typename Row>
+hipError_t spmm_sliced_chunks(const SlicedArgs& a, hipStream_t s) {
   if (a.n_dst == 0 || a.F == 0) return hipSuccess;
   // Row chunks: the 8 partial planes of a chunk (chunk_rows * n_slices * 4F bytes, <= ~32 MB) are
   // written and read back while still resident in the 256 MiB Infinity Cache, and the same
@@ -318,7 +192,7 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStrea
   for (int64_t r0 = 0; r0 < a.n_dst; r0 += chunk) {
     const int64_t r1 = r0 + chunk < a.n_dst ? r0 + chunk : a.n_dst;
     const int lpr = sliced_lpr(a.F, a.n_src, a.n_slices, a.n_dst, a.full_width, a.n_keep, a.x_bytes, tuning().sliced_lpr);
-    hipError_t err = gather(a, lpr, r0, r1, s);
+    hipError_t err = launch_gather<Row>(a, lpr, r0, r1, s);
     if (err != hipSuccess) return err;
     Epilogue ep = a.ep;  // rows of this chunk start at r0
     if (ep.mask != nullptr) ep.mask += r0 * ep.ldm;
@@ -329,12 +203,15 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStrea
   return hipSuccess;
 }
 
-hipError_t spmm_sliced_f32(const SlicedArgs& a, hipStream_t s) {
-  if (a.x_bytes != 4) return hipErrorInvalidValue;
+}  // namespace
+
+hipError_t spmm_sliced(const SlicedArgs& a, hipStream_t s) {
+  if (a.x_bytes != 4 && a.x_bytes != 2) return hipErrorInvalidValue;
+  if (a.x_bytes == 2 && a.src_scale != nullptr) return hipErrorInvalidValue;  // the source scale belongs to rows_to_bf16
   bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip)
   const hipError_t err = spmm_owned_try(a, s, &owned);
   if (err != hipSuccess || owned) return err;
-  return spmm_sliced_chunks(a, launch_gather_f32, s);
+  return a.x_bytes == 4 ? spmm_sliced_chunks<SlicedRowF32>(a, s) : spmm_sliced_chunks<SlicedRowBf16>(a, s);
 }
 
 }  // namespace dgmi

@@ -1,7 +1,10 @@
-// dgmi_sliced_common.h — what the two XCD-local SpMM translation units share (dgmi_sliced.hip: fp32 table;
-// dgmi_sliced_bf16.hip: bf16 table): constants, the plane-row store, the touch-ahead blocks, the launch geometry, the
-// column-pass rule and the chunk driver.  The two differ by the bytes of a gathered element (4 / 2), hence the columns a
-// lane owns (one 16-B load: 4 / 8) and the widest lane group (64 / 32: 256 columns either way).
+// dgmi_sliced_common.h — what the forms of the XCD-local SpMM share (the pair: dgmi_sliced.hip with the one gather body
+// of dgmi_sliced_kernel.h; the workgroup-owned form: dgmi_owned.hip), for an fp32 and for a bf16 table: constants, the
+// plane-row store, what the row policies of an element type have in common, the touch-ahead blocks, the launch geometry
+// and the column-pass rule.  The two tables differ by the bytes of a gathered element (4 / 2), hence the columns a lane
+// owns (one 16-B load: 4 / 8) and the widest lane group (64 / 32: 256 columns either way).  The host side (sliced_runs,
+// sliced_run, sliced_geometry, sliced_lpr) is also what a stand-alone host program includes
+// (tests/test_sliced_taper_host.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,13 +15,6 @@
 
 namespace dgmi {
 
-// The gather launch of one row chunk [row_begin, row_end) at lane-group width `lpr`, for the element type of a.X.
-typedef hipError_t (*SlicedGather)(const SlicedArgs& a, int lpr, int64_t row_begin, int64_t row_end, hipStream_t s);
-
-// The chunk driver (dgmi_sliced.hip): cuts [0, n_dst) into row chunks; per chunk picks the lane-group width
-// (sliced_lpr below), runs `gather` and then the plane reduce with the chunk's dst_scale / Y / mask offsets.
-hipError_t spmm_sliced_chunks(const SlicedArgs& a, SlicedGather gather, hipStream_t s);
-
 // The workgroup-owned form (dgmi_owned.hip): rows summed in LDS, no planes, bit-identical to the pair, from an fp32 or
 // a bf16 table.  *taken: the product was launched; false (and hipSuccess): the form does not take it and the caller
 // runs the pair.
@@ -27,10 +23,18 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken);
 namespace {
 
 constexpr int64_t kColumnPassMinRows = 32768;  // column passes only when a pass still has >= ~8k waves
-constexpr int kRowsPerGroup = 8;  // < LPR (row boundaries live one per lane of the group); per width: rows_per_group
 constexpr int64_t kTaperRows = 8192;  // rows at the end of a chunk that take shorter runs (sliced_runs, sliced_geometry)
 constexpr int kTouchLead = 24;   // worker blocks of a slice between a toucher and the blocks it touches for
 constexpr int kTouchGroup = 8;   // worker blocks per toucher block
+// Rows per lane group (< LPR: row boundaries live one per lane of the group): a speed knob only (the sums do not depend
+// on it).  The step of bench.py on the canonical-order kernels, ms of the four half-width (16-lane, two-pass) products /
+// of the four full-width (32-lane) ones at 2 / 3 / 4 / 6 / 8 / 12 / 15 rows (profiles/sliced_tail/README.md):
+//   no taper      1.344 / 1.345 / 1.359 / 1.385 / 1.407 / 1.460 / 1.484     1.058 / 1.014 / 0.989 / 0.970 / 0.971 / 0.982 / 0.991
+//   taper 8192    1.351 / 1.330 / 1.333 / 1.338 / 1.338                     1.072 / 1.020 / 0.997 / 0.969 / 0.961
+// Without the taper the half-width products want 2-3 rows and the full-width ones 6-8 (what the short runs gave the
+// half-width products was mostly a shorter drain); with it 8 rows are within 0.01 ms — half a run-to-run spread of the
+// step — of the best value of either width at any taper, so one value serves every width.
+constexpr int kRowsPerGroup = 8;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -42,32 +46,96 @@ __device__ __forceinline__ void store_plane_row(float* p, const float4& v) {
   __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
 }
 
-// Source row `idx` of the feature table.  OFF32: the table is < 4 GiB, so the byte offset fits 32 bits — one
-// v_mul_lo_u32 and a global_load with a scalar base and a 32-bit vector offset, instead of the six-instruction 64-bit
-// multiply-add chain a (int64 ldx) product costs per gathered row.
-template <bool OFF32>
-__device__ __forceinline__ float4 ld_row(const float* __restrict__ X, const float* __restrict__ Xc, int idx, int64_t ldx,
-                                         uint32_t row_bytes, uint32_t col_bytes) {
-  // X is the (wave-uniform) table base, Xc = X + this lane's column
-  if (OFF32) return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
-  return ld4(Xc + (int64_t)idx * ldx);
-}
+// What the row policies of the two forms of the XCD-local SpMM share, per element type of the gathered table (the pair:
+// SlicedRowF32 / SlicedRowBf16, dgmi_sliced_kernel.h; the workgroup-owned form: OwnedRowF32 / OwnedRowBf16,
+// dgmi_owned_kernel.h): the columns a lane owns, the registers of a gathered row, its load, the sums and the canonical
+// step acc + x / fmaf(w, x, acc).
+// An fp32 table: a lane owns 4 columns — one 16-B load, one float4 sum.
+struct RowF32 {
+  typedef float Elem;
+  typedef float4 Reg;  // a gathered row: this lane's columns
+  typedef float4 Acc;
+  static constexpr int kCols = 4;
+  static constexpr int kMaxLpr = 64;  // the widest lane group: 256 columns either way
+
+  static __device__ __forceinline__ Acc zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+  // Source row `idx` of the feature table.  OFF32: the table is < 4 GiB, so the byte offset fits 32 bits — one
+  // v_mul_lo_u32 and a global_load with a scalar base and a 32-bit vector offset, instead of the six-instruction 64-bit
+  // multiply-add chain a (int64 ldx) product costs per gathered row.  X is the (wave-uniform) table base, Xc = X + this
+  // lane's column.
+  template <bool OFF32>
+  static __device__ __forceinline__ Reg load(const Elem* __restrict__ X, const Elem* __restrict__ Xc, int idx, int64_t ldx,
+                                             uint32_t row_bytes, uint32_t col_bytes) {
+    if (OFF32) return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
+    return ld4(Xc + (int64_t)idx * ldx);
+  }
+
+  template <bool WEIGHTED>
+  static __device__ __forceinline__ void add(Acc& acc, float w, const Reg& x) {
+    if (WEIGHTED) {
+      acc.x = fmaf(w, x.x, acc.x);
+      acc.y = fmaf(w, x.y, acc.y);
+      acc.z = fmaf(w, x.z, acc.z);
+      acc.w = fmaf(w, x.w, acc.w);
+    } else {
+      acc.x += x.x;
+      acc.y += x.y;
+      acc.z += x.z;
+      acc.w += x.w;
+    }
+  }
+};
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
-// Source row `idx` of the bf16 table: this lane's 8 columns, one 16-B load.  OFF32: the table is < 4 GiB (see ld_row).
-template <bool OFF32>
-__device__ __forceinline__ v4u ld_row8(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Xc, int idx, int64_t ldx,
-                                       uint32_t row_bytes, uint32_t col_bytes) {
-  if (OFF32) return *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
-  return *reinterpret_cast<const v4u*>(Xc + (int64_t)idx * ldx);
-}
+// A bf16 table: a lane owns 8 columns — one 16-B load, each of its four dwords widened by a shift and a mask into the
+// two floats of one column PAIR.  The eight sums are kept as those four pairs, in two-element vectors: the adds are
+// packed adds (or packed fmas) of a widened dword onto its pair, element for element what acc + x / fmaf(w, x, acc)
+// give.  Left as eight scalars the compiler chooses the pairs of its packed adds itself, not always these, and moves
+// the sums between them (profiles/owned_one_body/README.md).
+struct RowBf16 {
+  typedef uint16_t Elem;
+  typedef v4u Reg;
+  typedef float v2f __attribute__((ext_vector_type(2)));
+  struct Acc {
+    v2f p[4];  // columns (0, 1), (2, 3), (4, 5), (6, 7)
+  };
+  static constexpr int kCols = 8;
+  static constexpr int kMaxLpr = 32;
 
-// bf16 -> fp32 is a shift (element 2k: the low half of dword k) or a mask (element 2k + 1): exact
-__device__ __forceinline__ float4 widen(uint32_t u0, uint32_t u1) {
-  return make_float4(__uint_as_float(u0 << 16), __uint_as_float(u0 & 0xffff0000u), __uint_as_float(u1 << 16),
-                     __uint_as_float(u1 & 0xffff0000u));
-}
+  static __device__ __forceinline__ Acc zero() { return Acc{{v2f(0.f), v2f(0.f), v2f(0.f), v2f(0.f)}}; }
+  static __device__ __forceinline__ Acc pairs(const float4& a, const float4& b) {
+    return Acc{{v2f{a.x, a.y}, v2f{a.z, a.w}, v2f{b.x, b.y}, v2f{b.z, b.w}}};
+  }
+  static __device__ __forceinline__ float4 half(const Acc& t, int h) {  // columns 4 h .. 4 h + 3
+    return make_float4(t.p[2 * h].x, t.p[2 * h].y, t.p[2 * h + 1].x, t.p[2 * h + 1].y);
+  }
+
+  // this lane's 8 columns of source row `idx`.  OFF32: see RowF32::load
+  template <bool OFF32>
+  static __device__ __forceinline__ Reg load(const Elem* __restrict__ X, const Elem* __restrict__ Xc, int idx, int64_t ldx,
+                                             uint32_t row_bytes, uint32_t col_bytes) {
+    if (OFF32) return *reinterpret_cast<const v4u*>(reinterpret_cast<const char*>(X) + ((uint32_t)idx * row_bytes + col_bytes));
+    return *reinterpret_cast<const v4u*>(Xc + (int64_t)idx * ldx);
+  }
+
+  // one dword onto its pair.  bf16 -> fp32 is a shift (element 2k: the low half of dword k) or a mask (element 2k + 1): exact
+  template <bool WEIGHTED>
+  static __device__ __forceinline__ void add_pair(v2f& acc, float w, uint32_t d) {
+    const v2f x = {__uint_as_float(d << 16), __uint_as_float(d & 0xffff0000u)};
+    if (WEIGHTED)
+      acc = __builtin_elementwise_fma(v2f(w), x, acc);
+    else
+      acc += x;
+  }
+
+  template <bool WEIGHTED>
+  static __device__ __forceinline__ void add(Acc& acc, float w, const Reg& x) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) add_pair<WEIGHTED>(acc.p[k], w, x[k]);
+  }
+};
 
 // Which destination rows a lane group sums.  A chunk's rows [0, n_rows) (relative to row_begin) are cut, in order, into
 // three sections of runs: the body in runs of `run[0]` = R rows, then — the tapered tail — the first half of the last
@@ -167,19 +235,6 @@ __device__ __forceinline__ bool touch_ahead(const int32_t* __restrict__ segptr, 
   return false;
 }
 
-// Rows per lane group, by lane-group width: a speed knob only (the sums do not depend on it).  The step of bench.py on
-// the canonical-order kernels, ms of the four half-width (16-lane, two-pass) products / of the four full-width (32-lane)
-// ones at 2 / 3 / 4 / 6 / 8 / 12 / 15 rows (profiles/sliced_tail/README.md):
-//   no taper      1.344 / 1.345 / 1.359 / 1.385 / 1.407 / 1.460 / 1.484     1.058 / 1.014 / 0.989 / 0.970 / 0.971 / 0.982 / 0.991
-//   taper 8192    1.351 / 1.330 / 1.333 / 1.338 / 1.338                     1.072 / 1.020 / 0.997 / 0.969 / 0.961
-// Without the taper the half-width products want 2-3 rows and the full-width ones 6-8 (what the short runs gave the
-// half-width products was mostly a shorter drain); with it 8 rows are within 0.01 ms — half a run-to-run spread of the
-// step — of the best value of either width at any taper, so one value serves every width.
-inline int rows_per_group(int lpr) {
-  (void)lpr;
-  return kRowsPerGroup;
-}
-
 // What one gather launch looks like on the host.
 struct SlicedGeometry {
   int R;                // rows per lane group (the body's; the tapered tail's are shorter)
@@ -206,7 +261,7 @@ inline SlicedGeometry sliced_geometry(int64_t row_begin, int64_t row_end, int64_
   // 2.366 ms (profiles/sliced_tail/README.md).  Never more than a quarter of the chunk (not measured: short runs cost the
   // full-width products up to 9 % when they cover all rows, the 2-row column above).
   const Tuning& tune = tuning();
-  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : rows_per_group(lpr);
+  const int rows_req = tune.sliced_rows > 0 ? tune.sliced_rows : kRowsPerGroup;
   g.R = rows_req < 1 ? 1 : (rows_req < lpr ? rows_req : lpr - 1);
   const int64_t quarter = (row_end - row_begin) / 4;
   const int64_t taper = tune.sliced_taper_rows < 0 ? 0

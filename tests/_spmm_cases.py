@@ -238,6 +238,13 @@ def one_at_a_time(n_dst):
     return out
 
 
+def no_off32_at_every_width():
+    """64-bit row addresses at every forced lane-group width: ``one_at_a_time`` takes ``sliced_no_off32`` at the built-in
+    width only, so a form that only those sweeps run never met the other widths' 64-bit kernels (a width the table's
+    element type does not have is ignored by the library: the built-in one)."""
+    return [dict(DEFAULTS, sliced_lpr=a, sliced_no_off32=1) for a in (8, 16, 32, 64)]
+
+
 def full_cross(n_dst, lpr):
     v = knob_values(n_dst)
     return [dict(sliced_lpr=lpr, sliced_rows=r, sliced_chunk_rows=c, sliced_no_off32=o, sliced_touch_lead=t)

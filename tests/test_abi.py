@@ -203,7 +203,7 @@ def test_no_launch_path_reads_the_environment():
     """the environment is read once (dgmi_api.hip `tuning()`, the kNN crossovers' static
     initialisers), never per launch; the product kernels carry no experiment switches."""
     csrc = os.path.join(ROOT, "dream_gnn_amd", "csrc")
-    for name in ("dgmi_sliced.hip", "dgmi_sliced_bf16.hip", "dgmi_sliced_common.h", "dgmi_select.hip", "dgmi_spmm.hip",
+    for name in ("dgmi_sliced.hip", "dgmi_sliced_bf16.hip", "dgmi_sliced_common.h", "dgmi_sliced_kernel.h", "dgmi_select.hip", "dgmi_spmm.hip",
                  "dgmi_plan.hip", "dgmi_compact.hip", "dgmi_csr.hip", "dgmi_sort.hip", "dgmi_edge.hip"):
         text = open(os.path.join(csrc, name)).read()
         assert "getenv" not in text, name

@@ -219,7 +219,7 @@ def test_other_slice_counts(dev, n_slices):
 # (3) every form of the kernel, zero tolerance
 # ---------------------------------------------------------------------------------------------
 FEW = [dict(C.DEFAULTS), dict(C.DEFAULTS, sliced_rows=3, sliced_chunk_rows=37, sliced_touch_lead=1),
-       dict(C.DEFAULTS, sliced_lpr=8, sliced_no_off32=1), dict(C.DEFAULTS, sliced_lpr=32, sliced_rows=31)]
+       dict(C.DEFAULTS, sliced_lpr=32, sliced_rows=31)] + C.no_off32_at_every_width()  # (64: not a bf16 width, the built-in one)
 
 
 @pytest.mark.parametrize("F", [8, 128, 344])
@@ -227,7 +227,8 @@ FEW = [dict(C.DEFAULTS), dict(C.DEFAULTS, sliced_rows=3, sliced_chunk_rows=37, s
 def test_every_form(dev, kind, F):
     """VALS 0 / 1 / 2, each plain, with dropout on the fly (Inf / NaN in the dead rows of the bf16 table) and on the
     compacted layout, with ``dst_scale`` and the epilogue; and the fp32 input route, ``gather_dtype=bfloat16`` with a
-    source scale in {0.5, 1, 2} folded into the conversion."""
+    source scale in {0.5, 1, 2} folded into the conversion.  ``FEW`` takes every width with 32-bit and with 64-bit row
+    addresses: all 36 instantiations of the bf16 gather are launched here."""
     _sweep(dev, 8, F, kind, False, FEW)
     _sweep(dev, 8, F, kind, True, FEW)
     _sweep(dev, 8, F, kind, True, FEW, compacted=True)

@@ -97,8 +97,9 @@ def _sweep(oracle, dev, n_slices, F, variant, settings):
 @pytest.mark.parametrize("variant", VARIANTS, ids=["%s%s%s" % (k, "-ss" if s else "", "-keep" if kp else "") for k, s, kp in VARIANTS])
 def test_sliced_every_variant_each_knob_alone_and_in_pairs(oracle, dev, variant, F):
     """All 12 template variants (unit / value stream / multiplicity x src_scale x dropout on the fly) at F = 4 / 128 /
-    344: the default launch, each knob alone, (lpr, rows), (chunk_rows, touch_lead) and a toucher in a later chunk."""
-    _sweep(oracle, dev, 8, F, variant, C.one_at_a_time(C.N_DST))
+    344: the default launch, each knob alone, (lpr, rows), (chunk_rows, touch_lead) and a toucher in a later chunk; then
+    64-bit row addresses at every width — with them every one of the 96 instantiations of the fp32 gather is launched."""
+    _sweep(oracle, dev, 8, F, variant, C.one_at_a_time(C.N_DST) + C.no_off32_at_every_width())
 
 
 @pytest.mark.parametrize("lpr", [0, 8, 16, 32, 64])
