@@ -151,6 +151,14 @@ ATTN_SIGNATURES = {
                                                                      ctypes.c_size_t, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/dgmi_scale.h (its own table, for the same reason).
+SCALE_SIGNATURES = {
+    "dgmi_spmm_owned_scaled_takes": (ctypes.c_int32, [_i64, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "dgmi_spmm_owned_scaled_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, _vp, _vp, _i64, _i64, _i64, _i64,
+                                                  ctypes.c_int32, ctypes.c_int32] + _EPI + [ctypes.POINTER(ctypes.c_int32), _vp]),
+}
+SCALE_CODE_SHIFT, SCALE_CODE_BITS = 17, 11  # DGMI_SCALE_CODE_SHIFT, DGMI_SCALE_CODE_BITS
+
 
 class DgmiError(RuntimeError):
     """A non-zero dgmi_status came back from the C ABI."""
@@ -166,8 +174,8 @@ def _load() -> ctypes.CDLL:
                               + list(ABOVE_SIGNATURES.items()) + list(BF16_SIGNATURES.items())
                               + list(GIVEN_SIGNATURES.items()) + list(CURVE_SIGNATURES.items())
                               + list(LAYOUT_SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
-                              + list(ATTN_SIGNATURES.items())):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export what the ten headers declare
+                              + list(ATTN_SIGNATURES.items()) + list(SCALE_SIGNATURES.items())):
+        fn = getattr(lib, name)  # AttributeError if the .so does not export what the eleven headers declare
         fn.restype = res
         fn.argtypes = args
     got = lib.dgmi_abi_version()
@@ -202,6 +210,28 @@ def sliced_layout_slices(n_dst: int, n_src: int, F: int, id_mult: bool = False) 
     """Source slices of the layout a plain fp32 XCD-local product of this shape should be given
     (``dgmi_sliced_layout_slices``: 8 but for the measured class; host arithmetic, no launch)."""
     return int(lib.dgmi_sliced_layout_slices(int(n_dst), int(n_src), int(F), 1 if id_mult else 0))
+
+
+def owned_scaled_takes(n_dst: int, n_src: int, F: int, ldx: int, n_slices: int, id_mult: bool, n_codes: int) -> bool:
+    """Whether ``dgmi_spmm_owned_scaled_f32`` would run this product (host arithmetic, no launch)."""
+    return bool(lib.dgmi_spmm_owned_scaled_takes(int(n_dst), int(n_src), int(F), int(ldx), int(n_slices), 1 if id_mult else 0,
+                                                 int(n_codes)))
+
+
+def spmm_owned_scaled(segptr, words, X, table, dst_scale, out, n_src: int, n_slices: int, id_mult: bool, epi) -> bool:
+    """``out = diag(dst_scale) A diag(table[code]) X`` on the owned form's scaled kernel (include/dgmi_scale.h) with the
+    coded id words ``words``, on the current stream of ``X``'s device.  The operands are what the caller has already
+    checked: float32, 16-byte aligned rows, one device.  False: declined, nothing was launched."""
+    act, slope, mask, mask_scale = epi
+    taken = ctypes.c_int32(0)
+    with torch.cuda.device(X.device):
+        check(lib.dgmi_spmm_owned_scaled_f32(
+            segptr.data_ptr(), words.data_ptr(), X.data_ptr(), X.stride(0), table.data_ptr(), table.numel(),
+            None if dst_scale is None else dst_scale.data_ptr(), out.data_ptr(), out.stride(0), out.shape[0], int(n_src),
+            X.shape[1], int(n_slices), 1 if id_mult else 0, int(act), float(slope), None if mask is None else mask.data_ptr(),
+            0 if mask is None else mask.stride(0), float(mask_scale), ctypes.byref(taken),
+            torch.cuda.current_stream(X.device).cuda_stream), "dgmi_spmm_owned_scaled_f32")
+    return taken.value == 1
 
 
 def check(status: int, what: str) -> None:

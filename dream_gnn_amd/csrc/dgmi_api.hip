@@ -9,6 +9,7 @@
 #include "dgmi_bf16.h"
 #include "dgmi_keep.h"
 #include "dgmi_layout.h"
+#include "dgmi_scale.h"
 #include "dgmi_kernels.h"
 #include "dgmi_tuning.h"
 
@@ -44,6 +45,7 @@ Tuning& tuning() {
     v.sliced_owned_lds_rows = env_ll("DGMI_SLICED_OWNED_LDS_ROWS", 0);
     v.sliced_owned_workers = (int)env_ll("DGMI_SLICED_OWNED_WORKERS", 0);
     v.sliced_owned_slices = (int)env_ll("DGMI_SLICED_OWNED_SLICES", 0);
+    v.sliced_owned_scaled = (int)env_ll("DGMI_SLICED_OWNED_SCALED", -1);
     v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
     v.sliced_owned_spin_ticks = env_ll("DGMI_SLICED_OWNED_SPIN_TICKS", 0);
     v.select_window_min = env_ll("DGMI_SELECT_WINDOW_MIN", 0);
@@ -76,6 +78,7 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_owned_lds_rows") == 0) t.sliced_owned_lds_rows = value;
   else if (strcmp(name, "sliced_owned_workers") == 0) t.sliced_owned_workers = (int)value;
   else if (strcmp(name, "sliced_owned_slices") == 0) t.sliced_owned_slices = (int)value;
+  else if (strcmp(name, "sliced_owned_scaled") == 0) t.sliced_owned_scaled = (int)value;
   else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;
   else if (strcmp(name, "sliced_owned_spin_ticks") == 0) t.sliced_owned_spin_ticks = value;
   else if (strcmp(name, "select_window_min") == 0) t.select_window_min = value;
@@ -387,6 +390,54 @@ DGMI_API int dgmi_spmm_sliced_bf16(const int32_t* segptr, const int32_t* indices
 
 DGMI_API int32_t dgmi_sliced_layout_slices(int64_t n_dst, int64_t n_src, int64_t F, int32_t id_multiplicity) {
   return dgmi::sliced_layout_slices(n_dst, n_src, F, id_multiplicity == 1);
+}
+
+// The arguments of the owned form's scaled product (include/dgmi_scale.h): no planes, no chunking.
+static dgmi::SlicedArgs scaled_args(const int32_t* segptr, const int32_t* coded, const float* X, int64_t ldx, const float* table,
+                                    int32_t n_codes, const float* dst_scale, float* Y, int64_t ldy, int64_t n_dst, int64_t n_src,
+                                    int64_t F, int32_t n_slices, int32_t id_multiplicity, const dgmi::Epilogue& ep) {
+  dgmi::SlicedArgs a{segptr, coded, nullptr, X, 4, ldx, nullptr, dst_scale, Y, ldy, n_dst, n_src, F, n_slices, nullptr, F, n_dst,
+                     nullptr, nullptr, 0, ep, false, id_multiplicity == 1};
+  a.scale_table = table;
+  a.n_codes = n_codes;
+  return a;
+}
+
+DGMI_API int32_t dgmi_spmm_owned_scaled_takes(int64_t n_dst, int64_t n_src, int64_t F, int64_t ldx, int32_t n_slices,
+                                              int32_t id_multiplicity, int32_t n_codes) {
+  if (n_dst < 1 || n_src < 1 || F < 1 || F % 4 != 0 || ldx < F || ldx % 4 != 0 || n_dst >= INT32_MAX || F > INT32_MAX ||
+      n_slices < 1 || n_slices > 64 || id_multiplicity < 0 || id_multiplicity > 1)
+    return 0;
+  static const float kSome = 0.f;  // never read: the query looks at whether a table is given, not at it
+  return dgmi::spmm_owned_scaled_takes(scaled_args(nullptr, nullptr, nullptr, ldx, &kSome, n_codes, nullptr, nullptr, F, n_dst,
+                                                   n_src, F, n_slices, id_multiplicity, {0, 0.f, nullptr, 0, 1.f}))
+             ? 1
+             : 0;
+}
+
+DGMI_API int dgmi_spmm_owned_scaled_f32(const int32_t* segptr, const int32_t* coded_indices, const float* X, int64_t ldx,
+                                        const float* table, int32_t n_codes, const float* dst_scale, float* Y, int64_t ldy,
+                                        int64_t n_dst, int64_t n_src, int64_t F, int32_t n_slices, int32_t id_multiplicity,
+                                        int32_t act, float act_slope, const float* out_mask, int64_t ld_mask,
+                                        float out_mask_scale, int32_t* taken, dgmi_stream_t stream) {
+  if (taken == nullptr) return DGMI_ERR_INVALID_ARG;
+  *taken = 0;
+  if (n_dst < 0 || n_src < 0 || F < 0 || n_slices < 1 || n_slices > 64 || !epilogue_ok(act, out_mask, ld_mask, F) ||
+      id_multiplicity < 0 || id_multiplicity > 1 || n_codes < 0)
+    return DGMI_ERR_INVALID_ARG;
+  if (out_mask != nullptr && (ld_mask % 4 != 0 || (reinterpret_cast<uintptr_t>(out_mask) & 15))) return DGMI_ERR_INVALID_ARG;
+  if (n_dst >= INT32_MAX || n_src >= INT32_MAX || F > INT32_MAX) return DGMI_ERR_TOO_LARGE;
+  if (n_dst == 0 || F == 0) return DGMI_OK;  // declined: the plain entry point returns at once for these
+  if (segptr == nullptr || coded_indices == nullptr || Y == nullptr || table == nullptr || X == nullptr) return DGMI_ERR_INVALID_ARG;
+  if (ldx < F || ldy < F || F % 4 != 0 || ldx % 4 != 0 || ldy % 4 != 0) return DGMI_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(Y) & 15)) return DGMI_ERR_INVALID_ARG;
+  if (static_cast<const void*>(X) == static_cast<const void*>(Y)) return DGMI_ERR_INVALID_ARG;
+  const dgmi::SlicedArgs a = scaled_args(segptr, coded_indices, X, ldx, table, n_codes, dst_scale, Y, ldy, n_dst, n_src, F,
+                                         n_slices, id_multiplicity, {act, act_slope, out_mask, ld_mask, out_mask_scale});
+  bool owned = false;
+  const hipError_t err = dgmi::spmm_owned_scaled(a, as_stream(stream), &owned);
+  *taken = err == hipSuccess && owned ? 1 : 0;
+  return from_hip(err);
 }
 
 DGMI_API int dgmi_gather_concat_f32(const int32_t* src, const int32_t* dst, int64_t E, const float* A,

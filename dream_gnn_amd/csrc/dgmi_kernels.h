@@ -133,6 +133,11 @@ hipError_t csr_sliced_from_csr_i32(const int32_t* indptr, const int32_t* indices
 constexpr int kMultShift = 28;
 constexpr int kMultMax = 7;                  // m - 1 <= 7
 constexpr uint32_t kMultIdMask = 0x0fffffffu;
+// The scale of the gathered row as a code in the id words (SlicedArgs::scale_table; include/dgmi_scale.h): bits 17..27
+// index a table of at most 2048 floats, ids are < 2^17; the multiplicity field and bit 31 stay where they are.
+constexpr int kScaleShift = 17;
+constexpr int kScaleBits = 11;
+constexpr uint32_t kScaleIdMask = (1u << kScaleShift) - 1u;
 
 struct SlicedArgs {
   const int32_t* segptr;   // n_slices * n_dst + 1
@@ -156,7 +161,18 @@ struct SlicedArgs {
   Epilogue ep;
   bool full_width;         // never split the columns into half-width passes (see sliced_lpr, dgmi_sliced_common.h)
   bool id_mult;            // vals == nullptr and the ids carry integer multiplicities (kMultShift)
+  // Non-null: the ids carry the code of the gathered row's scale (kScaleShift) and scale_table[code], n_codes entries,
+  // is that scale.  Only spmm_owned_try's scaled kernel masks such words (spmm_owned_scaled_takes): no other launch
+  // path may be given them.
+  const float* scale_table = nullptr;
+  int n_codes = 0;
 };
+
+// whether spmm_owned_try runs the product of these arguments (a.scale_table non-null) on its scaled kernel: host
+// arithmetic, no launch (dgmi_owned.hip)
+bool spmm_owned_scaled_takes(const SlicedArgs& a);
+// that product; *taken = false (and hipSuccess): declined, nothing was launched
+hipError_t spmm_owned_scaled(const SlicedArgs& a, hipStream_t s, bool* taken);
 
 // per row of a CSR with positive values: scale s and per-edge m in 1..8 with vals[p] = m * s to within rel_tol, or
 // *fail = 1 when some row has no such form (dgmi_edge.hip); mult[p] = m - 1

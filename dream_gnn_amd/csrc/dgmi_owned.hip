@@ -77,6 +77,42 @@ __global__ __launch_bounds__(kWave* kOwnedWaves, 4) void spmm_owned_bf16_kernel(
                                                                  lag, spin_ticks, workers, ep);
 }
 
+// An fp32 table whose id words carry the code of the gathered row's scale (SCALED, dgmi_owned_kernel.h;
+// include/dgmi_scale.h): the 16-wave form without a gate, 32-bit row offsets.  `table`: n_codes scales, copied into the
+// 2^kScaleBits floats of LDS the launch adds behind the plan's.
+constexpr size_t kOwnedScaleLdsBytes = sizeof(float) << kScaleBits;
+template <int LPR, int VALS>
+__global__ __launch_bounds__(kWave* kOwnedWaves, 4) void spmm_owned_scaled_kernel(
+    const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ X, int64_t ldx,
+    const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy, int64_t n_dst, int F, OwnedPlan pl, int workers,
+    Epilogue ep, const float* __restrict__ table, int n_codes) {
+  owned_body<OwnedRowF32, LPR, VALS, true, kOwnedWaves, false, true>(segptr, indices, X, ldx, dst_scale, Y, ldy, n_dst, F, pl, nullptr,
+                                                                     -1, 0, workers, ep, table, n_codes);
+}
+
+// The lane-group widths the scaled kernel is built at: those of the product classes it was measured on (F = 128 at
+// full and at half width).  Every other width is declined.
+constexpr bool owned_scaled_built(int lpr) { return lpr == 16 || lpr == 32; }
+
+template <int LPR>
+hipError_t launch_owned_scaled(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, hipStream_t s) {
+  const int workers = tuning().sliced_owned_workers > 0 && tuning().sliced_owned_workers < kOwnedWorkers ? tuning().sliced_owned_workers : 0;
+  const size_t lds = pl.lds_bytes + kOwnedScaleLdsBytes;
+#define DGMI_OWNED_SCALED(V)                                                                                              \
+  do {                                                                                                                    \
+    auto kern = &spmm_owned_scaled_kernel<LPR, V>;                                                                        \
+    static const hipError_t attr =                                                                                        \
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);  \
+    if (attr != hipSuccess) return attr;                                                                                  \
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave* kOwnedWaves), lds, s, a.segptr, a.indices,                 \
+                       static_cast<const float*>(a.X), a.ldx, a.dst_scale, a.Y, a.ldy, a.n_dst, (int)a.F, pl, workers, a.ep, \
+                       a.scale_table, a.n_codes);                                                                         \
+  } while (0)
+  if (a.id_mult) DGMI_OWNED_SCALED(2); else DGMI_OWNED_SCALED(0);
+#undef DGMI_OWNED_SCALED
+  return hipGetLastError();
+}
+
 template <typename Row, int LPR, int VALS, bool OFF32, int WAVES>
 constexpr auto owned_kernel() {
   if constexpr (std::is_same<Row, OwnedRowBf16>::value)
@@ -227,9 +263,45 @@ hipError_t launch_owned_width(const SlicedArgs& a, const OwnedPlan& pl, int lpr,
   }
 }
 
+// The classes of owned_class_form whose SCALED product (scale codes in the id words: no pre-scale pass, the scale out of
+// LDS) beat pre-scale pass + plain kernel inside the step of bench.py by more than the latter's min .. max spread
+// (profiles/owned_scale/README.md).  A class not named here keeps the pre-scale pass.
+bool owned_class_scaled(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+  const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (pl.slices == kOwnedSlices) {
+    if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return true;  // 50 000 sources -> 100 000 rows, unit values
+    if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return true;   // kNN-64 at 100 000 nodes
+    if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return true;   // kNN-64 at 50 000 nodes
+  }
+  if (pl.slices == kOwnedWideSlices && pl.col_rounds == 1 && pl.row_rounds == 1 && !id_mult && mib(48, 64)) return true;
+  return false;
+}
+
+// `launch` = false: the decision alone (*taken as a launch would leave it), nothing is launched.
+hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launch);
+
 }  // namespace
 
 hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
+  *taken = false;
+  if (a.scale_table != nullptr) return hipErrorInvalidValue;  // coded id words come in through spmm_owned_scaled only
+  return owned_try(a, s, taken, true);
+}
+
+bool spmm_owned_scaled_takes(const SlicedArgs& a) {
+  bool taken = false;
+  return a.scale_table != nullptr && owned_try(a, nullptr, &taken, false) == hipSuccess && taken;
+}
+
+hipError_t spmm_owned_scaled(const SlicedArgs& a, hipStream_t s, bool* taken) {
+  *taken = false;
+  if (a.scale_table == nullptr) return hipErrorInvalidValue;
+  return owned_try(a, s, taken, true);
+}
+
+namespace {
+
+hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launch) {
   *taken = false;
   const Tuning& tune = tuning();
   if (tune.sliced_owned == 0) return hipSuccess;
@@ -259,6 +331,21 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   if (tune.sliced_owned != 1 && rule == 0) return hipSuccess;
   const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * a.x_bytes < ((int64_t)1 << 32);
   bool resident = true;
+  if (a.scale_table != nullptr) {
+    // The scaled kernel: one form (16 waves, no gate, 32-bit offsets, an fp32 table) at the widths of its classes.  A
+    // product outside it — or of a class that keeps the pre-scale pass — is declined: nothing else masks a coded id word.
+    // (a forced owned form — sliced_owned = 1 — runs every product it can in that form, this one included)
+    const bool wanted = tune.sliced_owned_scaled == 1 ||
+                        (tune.sliced_owned_scaled < 0 && (tune.sliced_owned == 1 || (rule == 1 && owned_class_scaled(pl, a.id_mult, table_bytes))));
+    if (!wanted || a.x_bytes != 4 || a.n_src > ((int64_t)1 << kScaleShift) || a.n_codes < 1 || a.n_codes > (1 << kScaleBits) ||
+        !off32 || !owned_scaled_built(lpr) || pl.lds_bytes + kOwnedScaleLdsBytes > (size_t)(160 << 10) || tune.sliced_owned_lag >= 0 ||
+        tune.sliced_owned_wgs == 2)
+      return hipSuccess;
+    *taken = true;
+    if (!launch) return hipSuccess;
+    return lpr == 16 ? launch_owned_scaled<16>(a, pl, grid, s) : launch_owned_scaled<32>(a, pl, grid, s);
+  }
+  if (!launch) return hipSuccess;
   if (a.x_bytes == 2) {
     // The bf16 kernel is built in one form only — one 16-wave workgroup per CU, no phase gate — so sliced_owned_lag,
     // sliced_owned_spin_ticks and sliced_owned_wgs are ignored for a bf16 table, and without arrive counters nothing
@@ -285,6 +372,8 @@ hipError_t spmm_owned_try(const SlicedArgs& a, hipStream_t s, bool* taken) {
   }
   return launch_owned_width<OwnedRowF32, kOwnedWaves>(a, pl, lpr, grid, off32, lag, spin, s, &resident);
 }
+
+}  // namespace
 
 // The slice count of the layout a plain fp32 product of this shape should be given (include/dgmi_layout.h).  8 — the
 // pair's binding of a slice to an XCD — for everything but the class of owned_class_form that was measured on 16

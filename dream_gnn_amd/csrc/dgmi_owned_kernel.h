@@ -46,6 +46,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dgmi_owned_common.h"
 #include "dgmi_sliced_common.h"
 
@@ -138,18 +140,40 @@ struct OwnedRowBf16 : RowBf16 {
   }
 };
 
+// a * b rounded to fp32 on its own.  The multiply instruction itself: written as a * b — also as __fmul_rn(a, b), also
+// under `#pragma clang fp contract(off)` — the backend forms one v_pk_fma_f32 of it and the add that takes the product
+// (seen in the assembly), which rounds once where the pre-scaled table has rounded twice.  Not tried: building the
+// unit with -ffp-contract=off (it would reach every kernel of the unit, whose bits are pinned), and
+// __builtin_amdgcn_fmul_legacy (0 x inf is 0 there, not NaN).  The price: four v_mul_f32 where v_pk_mul_f32 would be two.
+__device__ __forceinline__ float owned_mul_rn(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 // VALS: 0 = unit edge values, 2 = multiplicities in the id words (dgmi_sliced.hip).  WAVES: waves of the workgroup, the
 // last one the toucher.  GATE: the phase gate is built (`arrive`, `lag` and `spin_ticks` are read under it only).
-template <typename Row, int LPR, int VALS, bool OFF32, int WAVES, bool GATE>
+//
+// SCALED: the id words carry, in bits kScaleShift .. kScaleShift + kScaleBits - 1, the CODE of the gathered row's scale
+// (dgmi_kernels.h; ids are < 2^kScaleShift): `table[code]` is diag(src_scale)'s entry of that row, so the product is
+// that of the table scaled row by row beforehand (scale_rows_f32) without the pass over it.  The workgroup copies the
+// table (at most 2^kScaleBits floats) into LDS behind its control words, in front of the barrier that follows their
+// zeroing.  An edge's scale is read from there when its gather is issued — one address per lane group: a broadcast —
+// and waits beside the row in a ring of W registers, which the hand-over carries like the row.  The row joins the sum
+// as s * x, rounded once (no contraction with the add or the multiplicity): bit for bit what the pre-scaled table
+// gives.  Nothing else differs: the task protocol, the toucher and write_rows read no id word.
+template <typename Row, int LPR, int VALS, bool OFF32, int WAVES, bool GATE, bool SCALED = false>
 __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices,
                                            const typename Row::Elem* __restrict__ X, int64_t ldx,
                                            const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy,
                                            int64_t n_dst, int F, OwnedPlan pl, unsigned* __restrict__ arrive, int lag,
-                                           int64_t spin_ticks, int workers, Epilogue ep) {
+                                           int64_t spin_ticks, int workers, Epilogue ep,
+                                           const float* __restrict__ table = nullptr, int n_codes = 0) {
   typedef typename Row::Elem Elem;
   typedef typename Row::Acc Acc;
   constexpr bool MULT = VALS == 2;
-  constexpr int kIdMask = MULT ? (int)kMultIdMask : 0x7fffffff;
+  constexpr int kIdMask = SCALED ? (int)kScaleIdMask : (MULT ? (int)kMultIdMask : 0x7fffffff);
+  static_assert(!SCALED || (std::is_same<Elem, float>::value && kScaleShift + kScaleBits <= kMultShift), "an fp32 table; the code lies below the multiplicity");
   constexpr int kRowSlots = Row::kLaneSlots * LPR;  // float4 slots of an LDS row
   // The window is handed from task to task (false: every run starts cold — the same bits).  Not in the two-workgroup
   // form: next to its 80 VGPRs the window and the next task's run do not stay in registers across the boundary.  Not
@@ -168,6 +192,10 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
   int* counter = phase_cnt + pl.phases;                                             // next task
   int* open = counter + 1;                                                          // highest phase the gate has opened
   for (int i = threadIdx.x; i < pl.tasks + pl.phases + 2; i += blockDim.x) done[i] = 0;
+  // every code has a word, whatever the table's length: a code is an LDS address inside the launch's allocation
+  float* lds_scale = reinterpret_cast<float*>(open + 1);  // [2^kScaleBits] (SCALED only: the launcher adds its bytes)
+  if (SCALED)
+    for (int i = threadIdx.x; i < (1 << kScaleBits); i += blockDim.x) lds_scale[i] = i < n_codes ? table[i] : 0.f;
   __syncthreads();
   const int total = pl.phases * T;
   const int label = (int)(blockIdx.x & 7u);
@@ -281,7 +309,8 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
   constexpr int W = kOwnedWindow;
   static_assert(W <= 8 && kMultShift == 28 && LPR % W == 0, "at most eight 4-bit multiplicity fields, shifted down from bit 28");
   typename Row::Reg v[W];
-  int idx[W];   // the ids of a group's W issues, read at its top: an issue is a multiply and a load
+  float sc[SCALED ? W : 1];  // SCALED: the scales of the W rows in flight
+  int idx[W];   // the ids of a group's W issues, read at its top: an issue is a multiply and a load (SCALED: id and code)
   int nidx[W];  // the ids of the W edges the last group of a run carries into the next task
   // The multiplicity fields of the W rows in flight wait in one register, the next edge's in bits 32 - 4 W ..: a
   // consumed field is shifted out, a new one comes in at bit 28.  Those of the W ids read at a group's top collect
@@ -294,15 +323,23 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
       int id = __shfl(batch_idx, gbase + u, kWave);
       if (MULT) {
         fields = (fields >> 4) | ((uint32_t)id & ((uint32_t)kMultMax << kMultShift));
-        id &= kIdMask;
+        if (!SCALED) id &= kIdMask;
       }
-      out[u] = id;
+      out[u] = id;  // SCALED: with its code, which issue() takes apart
     }
     if (MULT) asm volatile("" : "+v"(fields));  // really one register: not the W id words kept for their fields
   };
   auto read_ids = [&](int batch_idx) { read_batch(batch_idx, idx, mults_in); };
 
   const uint32_t row_bytes = (uint32_t)ldx * (uint32_t)sizeof(Elem);
+  // the gather of slot u — and, SCALED, the read of its scale — of the row id word `word` names
+  auto issue = [&](int u, const Elem* Xcol, int word, uint32_t cbytes) {
+    if (SCALED) {
+      sc[u] = lds_scale[((uint32_t)word >> kScaleShift) & ((1u << kScaleBits) - 1u)];
+      word &= kIdMask;
+    }
+    v[u] = Row::template load<OFF32>(X, Xcol, word, ldx, row_bytes, cbytes);
+  };
   int k = grab();
   OwnedWork w = owned_decode(pl, wg, T, k, grp);
   int e_begin = 0, e_end = 0;
@@ -319,7 +356,7 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
     if (L > 0 && !carried) {
       read_ids(nxt_idx);
 #pragma unroll
-      for (int u = 0; u < W; ++u) v[u] = Row::template load<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+      for (int u = 0; u < W; ++u) issue(u, Xc, idx[u], col_bytes);
       mults = mults_in;
     }
     const int k_next = grab();
@@ -371,7 +408,13 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
           m = (float)(((mults >> (32 - 4 * W)) & (uint32_t)kMultMax) + 1u);
           mults >>= 4;
         }
-        Row::template add<MULT>(acc, m, v[u]);
+        if constexpr (SCALED) {  // s * x rounded on its own, as the pre-scale pass stores it
+          const float s = sc[u];
+          const float4 t = make_float4(owned_mul_rn(s, v[u].x), owned_mul_rn(s, v[u].y), owned_mul_rn(s, v[u].z), owned_mul_rn(s, v[u].w));
+          Row::template add<MULT>(acc, m, t);
+        } else {
+          Row::template add<MULT>(acc, m, v[u]);
+        }
       };
       auto rows_before = [&](int p) {  // row(s) ended before edge p (empty rows commit zeros)
         while (p >= row_end) {
@@ -395,7 +438,7 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
         for (int u = 0; u < W; ++u) {
           rows_before(p0 + u);
           add(u);
-          v[u] = Row::template load<OFF32>(X, Xc, idx[u], ldx, row_bytes, col_bytes);
+          issue(u, Xc, idx[u], col_bytes);
           __builtin_amdgcn_sched_barrier(0);
         }
         mults = mults_in;
@@ -446,7 +489,7 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
             rows_before(p0 + u);
             add(u);
           }
-          v[u] = Row::template load<OFF32>(X, Xn, nidx[u], ldx, row_bytes, ncol_bytes);
+          issue(u, Xn, nidx[u], ncol_bytes);
           __builtin_amdgcn_sched_barrier(0);
         }
         mults = nmults;

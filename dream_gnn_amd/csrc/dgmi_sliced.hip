@@ -208,6 +208,7 @@ hipError_t spmm_sliced_chunks(const SlicedArgs& a, hipStream_t s) {
 hipError_t spmm_sliced(const SlicedArgs& a, hipStream_t s) {
   if (a.x_bytes != 4 && a.x_bytes != 2) return hipErrorInvalidValue;
   if (a.x_bytes == 2 && a.src_scale != nullptr) return hipErrorInvalidValue;  // the source scale belongs to rows_to_bf16
+  if (a.scale_table != nullptr) return hipErrorInvalidValue;  // coded id words: the pair's kernels do not mask them (dgmi_scale.h)
   bool owned = false;  // the plane-free form, where it applies and is selected (dgmi_owned.hip)
   const hipError_t err = spmm_owned_try(a, s, &owned);
   if (err != hipSuccess || owned) return err;

@@ -388,6 +388,13 @@ COMPACT_DROPPED = os.environ.get("DGMI_COMPACT_DROPPED", "1") != "0"
 MULT_FORM = os.environ.get("DGMI_MULT_FORM", "1") != "0"
 MULT_REL_TOL = 2.4e-7
 MULT_SHIFT, MULT_MAX_IDS = 28, 1 << 28
+# A scale of the gathered rows that is a node constant rides in the id words as well (include/dgmi_scale.h): bits 17..27
+# hold the code of its bit pattern, a table of at most 2048 patterns goes with the launch, ids are < 2^17 — for the
+# products the library's owned form runs scaled (`dgmi_spmm_owned_scaled_takes`), instead of their pre-scale pass.
+# DGMI_SCALE_CODES=0 switches it off (A/B, tests).
+SCALE_CODES = os.environ.get("DGMI_SCALE_CODES", "1") != "0"
+SCALE_SHIFT, SCALE_BITS = _lib.SCALE_CODE_SHIFT, _lib.SCALE_CODE_BITS
+SCALE_MAX_IDS, SCALE_MAX_CODES = 1 << SCALE_SHIFT, 1 << SCALE_BITS
 COLUMN_PASS_MIN_ROWS, LONG_ROW_MIN_DEGREE = 32768, 384                # the launcher's column-pass rule (dgmi_sliced.hip); see _few_long_rows
 SPLIT_MIN_DEGREE, SPLIT_DENSE_DEGREE = 8, 300                       # average degree (edges / rows) of the whole graph
 SPLIT_MAX_TABLE_BYTES, SPLIT_MAX_TABLE_BYTES_DENSE = 350_000_000, 900_000_000
@@ -423,7 +430,7 @@ class _Direction:
 class _Structure:
     """Everything about a CSRGraph that depends on the edge list only (shared by value views)."""
 
-    __slots__ = ("n_dst", "n_src", "dst", "src", "nnz", "planned", "validated", "wide", "fwd", "bwd")
+    __slots__ = ("n_dst", "n_src", "dst", "src", "nnz", "planned", "validated", "wide", "fwd", "bwd", "scale_builds")
 
 
 # the per-direction state under the names it had as loose slots: indptr .. split read the forward record, *_t the transposed
@@ -572,6 +579,7 @@ class CSRGraph:
         S.planned = planned
         S.wide = {}  # (transposed, n_slices) -> an XCD-sliced layout of another slice count than sliced / sliced_t have (_layout_of)
         S.validated = bool(check_range)
+        S.scale_builds = 0  # coded id words made for this structure's views (_scale_ids)
         # `regular`: no destination row is extremely long, so the XCD-local kernel (which walks a
         # (row, slice) segment sequentially) is safe to use.  Known after the one readback of a validated build
         # (below); for an unchecked build None = not known yet: decided — one readback of the maximum degree — at the
@@ -717,6 +725,53 @@ class CSRGraph:
     @staticmethod
     def _fold(scale, other):
         return scale if other is None else scale * other.reshape(-1)
+
+    @staticmethod
+    def scale_codes(scale: torch.Tensor, ids: torch.Tensor):
+        """``(table, words)`` for a float32 scale vector of at most ``SCALE_MAX_IDS`` entries and id words whose low
+        ``SCALE_SHIFT`` bits are ids into it: ``table`` lists the distinct BIT PATTERNS of ``scale`` (so ``-0.0``, ``+0.0``
+        and every NaN payload keep a code of their own) and ``words = ids | code[id] << SCALE_SHIFT``, whatever else the
+        words carry above bit ``SCALE_SHIFT + SCALE_BITS`` (the multiplicities).  ``(None, None)`` when ``scale`` has
+        more than ``SCALE_MAX_CODES`` patterns.  Reads one size back."""
+        if scale.dim() != 1 or scale.dtype != torch.float32 or scale.shape[0] > SCALE_MAX_IDS:
+            raise RuntimeError("scale_codes takes a 1-D float32 scale of at most %d entries" % SCALE_MAX_IDS)
+        bits, code = torch.unique(scale.contiguous().view(torch.int32), return_inverse=True)
+        if bits.shape[0] > SCALE_MAX_CODES:
+            return None, None
+        words = ids | (code.to(torch.int32)[(ids & (SCALE_MAX_IDS - 1)).long()] << SCALE_SHIFT)
+        return bits.view(torch.float32), words
+
+    def _scale_ids(self, name: str, scale: torch.Tensor, ids: torch.Tensor):
+        """``(table, coded id words)`` of layout ``name`` for the scale ``scale`` of its gathered rows, or None: the
+        scale bound to the id words ONCE per graph and scale (a node constant in real use: a degree normalisation), so
+        that the product needs no pass that scales ``X`` (include/dgmi_scale.h).  ``ids``: the layout's id words, with
+        the multiplicities where the view has them.
+
+        One entry per layout, kept with the view's values; a new scale replaces it.  The key is the scale's storage —
+        pointer, length, stride and version counter, with a reference held so that the pointer cannot be reused — hence
+        views of one tensor hit and an in-place update rebuilds.  Never inside a stream capture: the build reads a size
+        back, and a replayed graph may refresh the scale in place without a version bump.  The same holds outside a capture
+        for a scale written behind torch's back — its ``data_ptr()`` handed to a kernel through the C ABI: no version is
+        bumped, the coded words stay those of the old values; such a caller passes a new tensor.  Two rebuilds without a hit in
+        between (a caller that makes its scale anew per call) turn the route off for this view and layout."""
+        if self._capturing() or scale.dtype != torch.float32 or not scale.is_cuda or scale.dim() != 1 or scale.shape[0] > SCALE_MAX_IDS:
+            return None
+        slot = name + "/scale_ids"
+        entry = self._v.get(slot)
+        if entry is False:
+            return None
+        key = (scale.data_ptr(), scale.shape[0], scale.stride(0), scale._version)
+        if entry is not None and entry["key"] == key:
+            entry["misses"] = 0
+            return entry["coded"]
+        misses = 0 if entry is None else entry["misses"] + 1
+        if misses >= 2:
+            self._v[slot] = False  # the second miss in a row: this caller's scale is no constant
+            return None
+        table, words = self.scale_codes(scale, ids)
+        self._S.scale_builds += 1
+        self._v[slot] = {"key": key, "ref": scale, "misses": misses, "coded": None if table is None else (table, words)}
+        return self._v[slot]["coded"]
 
     def _combine_vals(self, name: str, split: "_SplitSliced"):
         """Second-stage values of a split layout for this view's edge values (made once per view and layout)."""
@@ -965,12 +1020,14 @@ class CSRGraph:
             # the bf16 gather stays on the pair's 8 slices: the library runs its owned form on them where it wins
             name, layout = self._layout_of(D) if bf16 else self._plain_layout(D, F, gathered_scale)
             mult = self._mult_ids(name, layout)
+            stable = None if gathered_scale is None else gathered_scale.reshape(-1)  # ONE tensor that outlives the call, or None
             if mult is not None:
                 # values = scale x multiplicity.  The scale is indexed by the destination ("row": D^-1 M) or by the source
                 # ("col": M D^-1): the output rows of one direction, the gathered rows of the other
                 if (mult[0] == "row") != D.transposed:
                     out_scale = self._fold(mult[1], out_scale)
                 else:
+                    stable = mult[1] if gathered_scale is None else None  # folded anew per call: no constant
                     gathered_scale = self._fold(mult[1], gathered_scale)
             gd = None
             if bf16:
@@ -983,6 +1040,10 @@ class CSRGraph:
             c = self._compacted(name, layout, mult)
             if c is not None:
                 return c.spmm(X, gathered_scale, out_scale, out, epi=epi, gather_dtype=gd)
+            if stable is not None and not bf16 and self._keep is None and (mult is not None or self._coo_vals is None):
+                y = self._scaled_product(name, layout, X, stable, mult, out_scale, out, epi)
+                if y is not None:
+                    return y
             if mult is not None:
                 return layout.spmm(X, gathered_scale, out_scale, out, vals=None, keep=self._keep, epi=epi, indices=mult[2],
                                    id_mult=True, gather_dtype=gd)
@@ -998,6 +1059,40 @@ class CSRGraph:
                               out, None if c is not None else self._vals_for(D.split_key, split.sliced.eid), keep=self._keep,
                               epi=epi, compacted=c, c_vals=self._combine_vals(D.split_key, split))
         return self._run(D, X, gathered_scale, out_scale, out, epi)
+
+    def _scaled_product(self, name, layout, X, scale, mult, out_scale, out, epi):
+        """The plain float32 product of ``layout`` with the single stable ``scale`` on its gathered rows through the
+        owned form's scaled kernel and coded id words (:meth:`_scale_ids`), or None — the caller then runs the pre-scale
+        pass and the plain product, as for every product the library declines (``dgmi_spmm_owned_scaled_takes``), for a
+        scale of too many patterns, inside a capture, and where the pass would not have been made either."""
+        F = X.shape[1]
+        if not SCALE_CODES or layout.n_src > SCALE_MAX_IDS or scale.shape[0] != layout.n_src or X.shape[0] != layout.n_src:
+            return None
+        if not X.is_cuda or X.device != layout.segptr.device or scale.device != X.device:
+            return None  # the plain path raises its error for operands on another device
+        if self._v.get(name + "/scale_ids") is False or not layout._prescale_pays(layout.n_src * F * 4, False):
+            return None
+        takes = lambda n: _lib.owned_scaled_takes(layout.n_dst, layout.n_src, F, X.stride(0), layout.n_slices, mult is not None, n)
+        if not takes(1):
+            return None
+        act, slope, mask, mask_scale = epi or _NO_EPI
+        if mask is not None and not (mask.dtype == torch.float32 and mask.dim() == 2 and tuple(mask.shape) == (layout.n_dst, F)
+                                     and mask.device == X.device and mask.stride(1) == 1 and mask.stride(0) % 4 == 0
+                                     and mask.data_ptr() % 16 == 0):
+            return None
+        coded = self._scale_ids(name, scale, layout.indices if mult is None else mult[2])
+        if coded is None or not takes(coded[0].shape[0]):
+            return None
+        ds = _prep_scale(out_scale, layout.n_dst, "dst_scale")
+        if ds is not None and (not ds.is_cuda or ds.device != X.device):
+            return None
+        y = torch.empty((layout.n_dst, F), dtype=torch.float32, device=X.device) if out is None else out
+        if tuple(y.shape) != (layout.n_dst, F) or y.dtype != torch.float32 or y.device != X.device:
+            return None
+        if not _lib.spmm_owned_scaled(layout.segptr, coded[1], X, coded[0], ds, y, layout.n_src, layout.n_slices,
+                                      mult is not None, (act, slope, mask, mask_scale)):
+            return None
+        return y
 
     def spmm(self, X, src_scale=None, dst_scale=None, out=None, epi=None, gather_dtype=None):
         """``diag(dst_scale) A diag(src_scale) X`` (no autograd).  Picks the XCD-local sliced kernel when the
