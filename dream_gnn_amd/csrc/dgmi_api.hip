@@ -46,6 +46,9 @@ Tuning& tuning() {
     v.sliced_owned_workers = (int)env_ll("DGMI_SLICED_OWNED_WORKERS", 0);
     v.sliced_owned_slices = (int)env_ll("DGMI_SLICED_OWNED_SLICES", 0);
     v.sliced_owned_scaled = (int)env_ll("DGMI_SLICED_OWNED_SCALED", -1);
+    v.sliced_owned_duty = (int)env_ll("DGMI_SLICED_OWNED_DUTY", -1);
+    v.sliced_owned_duty_chunk = (int)env_ll("DGMI_SLICED_OWNED_DUTY_CHUNK", 0);
+    v.sliced_owned_duty_lead = (int)env_ll("DGMI_SLICED_OWNED_DUTY_LEAD", 0);
     v.sliced_owned_lag = (int)env_ll("DGMI_SLICED_OWNED_LAG", -2);
     v.sliced_owned_spin_ticks = env_ll("DGMI_SLICED_OWNED_SPIN_TICKS", 0);
     v.select_window_min = env_ll("DGMI_SELECT_WINDOW_MIN", 0);
@@ -79,6 +82,9 @@ DGMI_API int dgmi_set_tuning(const char* name, int64_t value) {
   else if (strcmp(name, "sliced_owned_workers") == 0) t.sliced_owned_workers = (int)value;
   else if (strcmp(name, "sliced_owned_slices") == 0) t.sliced_owned_slices = (int)value;
   else if (strcmp(name, "sliced_owned_scaled") == 0) t.sliced_owned_scaled = (int)value;
+  else if (strcmp(name, "sliced_owned_duty") == 0) t.sliced_owned_duty = (int)value;
+  else if (strcmp(name, "sliced_owned_duty_chunk") == 0) t.sliced_owned_duty_chunk = (int)value;
+  else if (strcmp(name, "sliced_owned_duty_lead") == 0) t.sliced_owned_duty_lead = (int)value;
   else if (strcmp(name, "sliced_owned_lag") == 0) t.sliced_owned_lag = (int)value;
   else if (strcmp(name, "sliced_owned_spin_ticks") == 0) t.sliced_owned_spin_ticks = value;
   else if (strcmp(name, "select_window_min") == 0) t.select_window_min = value;

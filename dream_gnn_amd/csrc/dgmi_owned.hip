@@ -24,6 +24,12 @@
 // kernel is short of waves (12 instead of 16 per CU: +17-23 %), yet 512 free-running workgroups drift over more slices
 // than 256 and lose in L2 misses more than the waves return, so the built-in rule selects the second form for no class.
 //
+// The DUTY form (spmm_owned_duty_kernel below; owned_body<..., DUTY>, dgmi_owned_kernel.h) has no toucher: all 16 waves
+// take tasks, and once per phase the wave that reserves the phase's first task touches the boundaries and ids of the
+// next phase.  It is what the four fp32 classes of the step run (owned_class_duty; profiles/owned_duty/README.md);
+// everything it is not built for — other widths, 64-bit offsets, a gate, the two-workgroup form, a bf16 table — keeps
+// the toucher.
+//
 // A bf16 table (x_bytes == 2) takes the same form through the same launcher (spmm_owned_try) and the same plan with 8
 // columns per lane; its kernel — the 16-wave form without a gate — is spmm_owned_bf16_kernel below, its classes are
 // owned_class_form's for x_bytes == 2.
@@ -90,27 +96,67 @@ __global__ __launch_bounds__(kWave* kOwnedWaves, 4) void spmm_owned_scaled_kerne
                                                                      -1, 0, workers, ep, table, n_codes);
 }
 
-// The lane-group widths the scaled kernel is built at: those of the product classes it was measured on (F = 128 at
-// full and at half width).  Every other width is declined.
+// The DUTY form (dgmi_owned_kernel.h): sixteen workers, no toucher — the touching is a duty of every `duty_chunk`-th
+// task slot, `duty_lead` slots ahead.  Built where the step of bench.py runs the form: an fp32 table, 32-bit offsets,
+// 16 waves, no gate, the widths of the measured classes; plain (`table` == nullptr) and SCALED.  A bf16 table keeps its
+// toucher: its kernels have not been measured in this form.
+template <int LPR, int VALS, bool SCALED>
+__global__ __launch_bounds__(kWave* kOwnedWaves, 4) void spmm_owned_duty_kernel(
+    const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices, const float* __restrict__ X, int64_t ldx,
+    const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy, int64_t n_dst, int F, OwnedPlan pl, int workers,
+    Epilogue ep, const float* __restrict__ table, int n_codes, int duty_chunk, int duty_lead) {
+  owned_body<OwnedRowF32, LPR, VALS, true, kOwnedWaves, false, SCALED, true>(segptr, indices, X, ldx, dst_scale, Y, ldy, n_dst, F, pl,
+                                                                             nullptr, -1, 0, workers, ep, table, n_codes, duty_chunk,
+                                                                             duty_lead);
+}
+
+// The lane-group widths the scaled kernel — and the duty form, scaled or not — is built at: those of the product
+// classes it was measured on (F = 128 at full and at half width).  Every other width is declined (the duty form: runs
+// with a toucher).
 constexpr bool owned_scaled_built(int lpr) { return lpr == 16 || lpr == 32; }
+constexpr bool owned_duty_built(int lpr) { return owned_scaled_built(lpr); }
+
+// The worker waves of a workgroup that take tasks (Tuning::sliced_owned_workers; 0: all `all` of them).
+int owned_tuned_workers(int all) {
+  const int w = tuning().sliced_owned_workers;
+  return w > 0 && w < all ? w : 0;
+}
+
+// One launch of a kernel with the scaled kernel's parameter list (and `extra` behind it), `lds` bytes of dynamic LDS.
+template <auto KERN, typename... Extra>
+hipError_t launch_owned_tabled(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, size_t lds, int workers, hipStream_t s,
+                               Extra... extra) {
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(KERN, dim3((unsigned)grid), dim3(kWave* kOwnedWaves), lds, s, a.segptr, a.indices,
+                     static_cast<const float*>(a.X), a.ldx, a.dst_scale, a.Y, a.ldy, a.n_dst, (int)a.F, pl, workers, a.ep,
+                     a.scale_table, a.n_codes, extra...);
+  return hipGetLastError();
+}
 
 template <int LPR>
 hipError_t launch_owned_scaled(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, hipStream_t s) {
-  const int workers = tuning().sliced_owned_workers > 0 && tuning().sliced_owned_workers < kOwnedWorkers ? tuning().sliced_owned_workers : 0;
   const size_t lds = pl.lds_bytes + kOwnedScaleLdsBytes;
-#define DGMI_OWNED_SCALED(V)                                                                                              \
-  do {                                                                                                                    \
-    auto kern = &spmm_owned_scaled_kernel<LPR, V>;                                                                        \
-    static const hipError_t attr =                                                                                        \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);  \
-    if (attr != hipSuccess) return attr;                                                                                  \
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWave* kOwnedWaves), lds, s, a.segptr, a.indices,                 \
-                       static_cast<const float*>(a.X), a.ldx, a.dst_scale, a.Y, a.ldy, a.n_dst, (int)a.F, pl, workers, a.ep, \
-                       a.scale_table, a.n_codes);                                                                         \
-  } while (0)
-  if (a.id_mult) DGMI_OWNED_SCALED(2); else DGMI_OWNED_SCALED(0);
-#undef DGMI_OWNED_SCALED
-  return hipGetLastError();
+  const int workers = owned_tuned_workers(kOwnedWorkers);
+  if (a.id_mult) return launch_owned_tabled<&spmm_owned_scaled_kernel<LPR, 2>>(a, pl, grid, lds, workers, s);
+  return launch_owned_tabled<&spmm_owned_scaled_kernel<LPR, 0>>(a, pl, grid, lds, workers, s);
+}
+
+// The duty form, plain (a.scale_table == nullptr: no table in LDS) or scaled; `pl`: the plan of kOwnedDutyWorkers workers.
+template <int LPR>
+hipError_t launch_owned_duty(const SlicedArgs& a, const OwnedPlan& pl, int64_t grid, hipStream_t s) {
+  // built-in: a duty per phase, one phase ahead (dgmi_owned_common.h)
+  const int chunk = tuning().sliced_owned_duty_chunk > 0 ? tuning().sliced_owned_duty_chunk : pl.tasks;
+  const int lead = tuning().sliced_owned_duty_lead > 0 ? tuning().sliced_owned_duty_lead : chunk;
+  const int workers = owned_tuned_workers(kOwnedDutyWorkers);
+  if (a.scale_table != nullptr) {
+    const size_t lds = pl.lds_bytes + kOwnedScaleLdsBytes;
+    if (a.id_mult) return launch_owned_tabled<&spmm_owned_duty_kernel<LPR, 2, true>>(a, pl, grid, lds, workers, s, chunk, lead);
+    return launch_owned_tabled<&spmm_owned_duty_kernel<LPR, 0, true>>(a, pl, grid, lds, workers, s, chunk, lead);
+  }
+  if (a.id_mult) return launch_owned_tabled<&spmm_owned_duty_kernel<LPR, 2, false>>(a, pl, grid, pl.lds_bytes, workers, s, chunk, lead);
+  return launch_owned_tabled<&spmm_owned_duty_kernel<LPR, 0, false>>(a, pl, grid, pl.lds_bytes, workers, s, chunk, lead);
 }
 
 template <typename Row, int LPR, int VALS, bool OFF32, int WAVES>
@@ -277,6 +323,20 @@ bool owned_class_scaled(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) 
   return false;
 }
 
+// The classes of owned_class_form whose product, inside the step of bench.py, is faster in the duty form than with a
+// toucher by more than the toucher form's min .. max spread (profiles/owned_duty/README.md).
+// All four fp32 classes of owned_class_form cleared that, plain and scaled.
+bool owned_class_duty(const OwnedPlan& pl, bool id_mult, int64_t table_bytes) {
+  const auto mib = [&](int64_t lo, int64_t hi) { return table_bytes >= (lo << 20) && table_bytes <= (hi << 20); };
+  if (pl.slices == kOwnedSlices) {
+    if (pl.col_rounds == 1 && pl.row_rounds == 2 && !id_mult && mib(16, 32)) return true;  // 50 000 sources -> 100 000 rows, unit values
+    if (pl.col_rounds == 2 && pl.row_rounds == 1 && id_mult && mib(48, 64)) return true;   // kNN-64 at 100 000 nodes
+    if (pl.col_rounds == 1 && pl.row_rounds == 1 && id_mult && mib(16, 32)) return true;   // kNN-64 at 50 000 nodes
+  }
+  if (pl.slices == kOwnedWideSlices && pl.col_rounds == 1 && pl.row_rounds == 1 && !id_mult && mib(48, 64)) return true;  // 100 000 sources -> 50 000 rows
+  return false;
+}
+
 // `launch` = false: the decision alone (*taken as a launch would leave it), nothing is launched.
 hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launch);
 
@@ -331,6 +391,17 @@ hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launc
   if (tune.sliced_owned != 1 && rule == 0) return hipSuccess;
   const bool off32 = !tune.sliced_no_off32 && (a.n_src * a.ldx + a.F) * a.x_bytes < ((int64_t)1 << 32);
   bool resident = true;
+  // The duty form (sixteen workers, no toucher): where it is built — an fp32 table, 32-bit offsets, the widths of the
+  // measured classes — and nothing asks for what only the toucher form has (a gate, the two-workgroup form), for
+  // sliced_owned_duty = 1 or a class of owned_class_duty.  Its plan is the same plan with the tasks-per-phase target of
+  // 16 workers; should that one not fit, the toucher form runs.
+  const int lag = tune.sliced_owned_lag >= -1 ? tune.sliced_owned_lag : kOwnedLag;
+  OwnedPlan pl_duty{};
+  if (a.x_bytes == 4 && off32 && owned_duty_built(lpr) && lag < 0 && tune.sliced_owned_wgs != 2 && rule != 2 &&
+      (tune.sliced_owned_duty == 1 || (tune.sliced_owned_duty < 0 && rule == 1 && owned_class_duty(pl, a.id_mult, table_bytes)))) {
+    pl_duty = owned_plan(a.n_dst, a.F, lpr, grid, tune.sliced_owned_rows, tune.sliced_owned_lds_rows, 1, phase_tasks, slices, cols, kOwnedDutyWorkers);
+    if (pl_duty.lds_bytes + (a.scale_table != nullptr ? kOwnedScaleLdsBytes : 0) > (size_t)(160 << 10)) pl_duty.ok = false;
+  }
   if (a.scale_table != nullptr) {
     // The scaled kernel: one form (16 waves, no gate, 32-bit offsets, an fp32 table) at the widths of its classes.  A
     // product outside it — or of a class that keeps the pre-scale pass — is declined: nothing else masks a coded id word.
@@ -343,6 +414,7 @@ hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launc
       return hipSuccess;
     *taken = true;
     if (!launch) return hipSuccess;
+    if (pl_duty.ok) return lpr == 16 ? launch_owned_duty<16>(a, pl_duty, grid, s) : launch_owned_duty<32>(a, pl_duty, grid, s);
     return lpr == 16 ? launch_owned_scaled<16>(a, pl, grid, s) : launch_owned_scaled<32>(a, pl, grid, s);
   }
   if (!launch) return hipSuccess;
@@ -353,6 +425,10 @@ hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launc
     *taken = true;
     return launch_owned_width<OwnedRowBf16, kOwnedWaves>(a, pl, lpr, grid, off32, -1, 0, s, &resident);
   }
+  if (pl_duty.ok) {  // no gate, hence no arrive counters: nothing is asked of the plane workspace
+    *taken = true;
+    return lpr == 16 ? launch_owned_duty<16>(a, pl_duty, grid, s) : launch_owned_duty<32>(a, pl_duty, grid, s);
+  }
   // the arrive counters live in the first bytes of the caller's plane workspace (n_slices * n_dst * ldp floats)
   const auto arrive_fits = [&](const OwnedPlan& p) {
     return sizeof(unsigned) * 8 * (size_t)p.phases <= sizeof(float) * (size_t)a.n_slices * (size_t)a.n_dst * (size_t)a.ldp;
@@ -360,7 +436,6 @@ hipError_t owned_try(const SlicedArgs& a, hipStream_t s, bool* taken, bool launc
   if (!arrive_fits(pl)) return hipSuccess;
   const int form = tune.sliced_owned_wgs == 1 || tune.sliced_owned_wgs == 2 ? tune.sliced_owned_wgs : (rule == 2 ? 2 : 1);
   const int64_t spin = tune.sliced_owned_spin_ticks > 0 ? tune.sliced_owned_spin_ticks : kOwnedSpinTicks;
-  const int lag = tune.sliced_owned_lag >= -1 ? tune.sliced_owned_lag : kOwnedLag;
   *taken = true;
   if (form == 2) {
     const int64_t grid2 = tune.sliced_owned_grid > 0 ? grid : 2 * grid;

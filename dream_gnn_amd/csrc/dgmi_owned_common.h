@@ -21,8 +21,9 @@ namespace dgmi {
 
 constexpr int kOwnedSlices = 8;                     // the slice count of a plan made without one (one slice per XCD, as the pair's layouts)
 constexpr int kOwnedMaxSlices = 64;                 // what the layout builders take
-constexpr int kOwnedWaves = 16;                     // waves per workgroup: 15 workers and the toucher
-constexpr int kOwnedWorkers = kOwnedWaves - 1;
+constexpr int kOwnedWaves = 16;                     // waves per workgroup: 15 workers and the toucher, or (the duty form) 16 workers
+constexpr int kOwnedWorkers = kOwnedWaves - 1;      // ... of the form with a toucher: the worker count the tasks-per-phase targets are stated for
+constexpr int kOwnedDutyWorkers = kOwnedWaves;      // ... of the duty form (owned_duty_*, at the end)
 constexpr int kOwnedPairWaves = 12;                 // the two-workgroups-per-CU form: 2 x (11 workers and a toucher)
 constexpr int64_t kOwnedLdsRowBytes = 144 << 10;    // LDS budget of the partial rows (the CU has 160 KiB)
 constexpr int kOwnedMaxPhases = 128;                // per-phase words live in LDS and in the arrive counters
@@ -62,17 +63,21 @@ struct OwnedTask {
 // `phase_tasks_target`: the built-in R's aim for 15 workers (the launcher passes kOwnedPhaseTasksMult for the kNN-64 classes);
 // `slices`: the slice count of the layout, 1 .. kOwnedMaxSlices; `cols_per_lane`: the columns a lane owns — 4 of an fp32
 // table, 8 of a bf16 one (OwnedRowBf16, dgmi_owned_kernel.h): a column round is cols_per_lane lpr columns wide, and a row of it costs
-// 4 cols_per_lane lpr bytes of LDS (the sums are fp32 either way).
+// 4 cols_per_lane lpr bytes of LDS (the sums are fp32 either way); `workers`: the waves of a workgroup that take tasks
+// — 0: all but a toucher (15, or 11 of the two-workgroup form), kOwnedDutyWorkers: the duty form's 16 — to which the
+// tasks-per-phase target is scaled.
 __host__ __device__ constexpr int owned_form_waves(int wgs_per_cu) { return wgs_per_cu == 2 ? kOwnedPairWaves : kOwnedWaves; }
 
 __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lpr, int64_t grid, int R_req, int64_t lds_rows_cap,
                                                 int wgs_per_cu = 1, int phase_tasks_target = kOwnedPhaseTasks,
-                                                int slices = kOwnedSlices, int cols_per_lane = 4) {
+                                                int slices = kOwnedSlices, int cols_per_lane = 4, int workers = 0) {
   OwnedPlan p{};
   p.ok = false;
   p.n_dst = n_dst;
+  if (workers == 0) workers = owned_form_waves(wgs_per_cu) - 1;  // a form with a toucher
   if (n_dst < 1 || F < 1 || grid < 1 || (wgs_per_cu != 1 && wgs_per_cu != 2) || (lpr != 8 && lpr != 16 && lpr != 32 && lpr != 64) ||
-      slices < 1 || slices > kOwnedMaxSlices || (cols_per_lane != 4 && cols_per_lane != 8))
+      slices < 1 || slices > kOwnedMaxSlices || (cols_per_lane != 4 && cols_per_lane != 8) || workers < 1 ||
+      workers > owned_form_waves(wgs_per_cu))
     return p;
   p.lpr = lpr;
   p.slices = slices;
@@ -89,8 +94,8 @@ __host__ __device__ inline OwnedPlan owned_plan(int64_t n_dst, int64_t F, int lp
   p.phases = p.col_rounds * p.row_rounds * slices;
   int R = R_req;
   if (R <= 0) {
-    // 1.6 tasks per worker wave: 24 for 15 workers, 18 for 11
-    const int phase_tasks = (phase_tasks_target * (owned_form_waves(wgs_per_cu) - 1) + kOwnedWorkers / 2) / kOwnedWorkers;
+    // 1.6 tasks per worker wave: 24 for 15 workers, 18 for 11, 26 for the duty form's 16
+    const int phase_tasks = (phase_tasks_target * workers + kOwnedWorkers / 2) / kOwnedWorkers;
     R = (p.round_rows + phase_tasks * p.G / 2) / (phase_tasks * p.G);  // rounded to nearest
     if (R > kOwnedMaxRows) R = kOwnedMaxRows;
   }
@@ -217,5 +222,81 @@ __host__ __device__ constexpr int owned_carry_read_group(int L_a) { return owned
 
 // The id batch of B that its id register holds when a run starts (carried or cold): the one its group 0 reads.
 __host__ __device__ constexpr int owned_carry_start_batch() { return owned_window_issue_batch(0); }
+
+// The touching.  The workers issue no cold load of boundaries or ids: somebody reads one word per 128-B line of both a
+// few task slots ahead of the task counter, CHUNK by chunk.  Chunk c of a workgroup with T task slots per phase is the
+// task slots [t0, t0 + chunk) of phase P, c = P owned_touch_chunks(T, chunk) + t0 / chunk: consecutive rows
+// [r_first, r_last) of one slice (owned_touch_rows), hence one run of boundaries — the words r_first .. r_last of the
+// slice's segptr, touched at r_first, at r_last and every 32 words from r_first (owned_touch_boundary) — and one run of
+// ids, [segptr[r_first], segptr[r_last]), touched every 32 words from its start (owned_touch_id).
+// In the form with a toucher the last wave does that for chunk after chunk, as soon as the task counter is within
+// kOwnedTouchLead slots of the chunk's first (dgmi_owned_kernel.h).  In the DUTY form every wave is a worker and the
+// touching is a duty of task slots: the wave that reserves the first slot of chunk c (owned_duty_chunk) touches, before
+// anything else, the chunks of owned_duty_span — chunk c + lead_chunks, the first duty also the chunks 0 .. lead_chunks
+// in front of it — and then goes on as any worker.  Every chunk of the launch is touched by exactly one duty, a chunk
+// past the last one by none, and a slot past the last task carries none.
+// The kernel and the host test (tests/test_owned_duty_host.py) take all of this from the functions below.
+constexpr int kOwnedTouchChunk = 4;      // task slots the toucher touches for at a time
+constexpr int kOwnedTouchLead = 8;       // task slots between the counter and the first slot of the chunk it touches for
+constexpr int kOwnedTouchLineWords = 32;  // 128 B of int32 words
+// The duty form's built-in chunk is a WHOLE PHASE — the plan's task slots, OwnedPlan::tasks: one duty per phase, by the
+// wave that reserves the phase's first task — and its lead one phase (measured: profiles/owned_duty/README.md — the
+// fewer duties the better, from 4 slots per duty, which gains nothing over the toucher, to a phase per duty).
+
+__host__ __device__ constexpr int owned_touch_chunks(int T, int chunk) { return (T + chunk - 1) / chunk; }  // per phase
+
+struct OwnedTouchRows {
+  bool any;                  // false: a short last round has none of the chunk's rows
+  int slice;
+  int64_t r_first, r_last;   // destination rows [r_first, r_last): boundary words r_first .. r_last of the slice
+};
+
+__host__ __device__ inline OwnedTouchRows owned_touch_rows(const OwnedPlan& pl, int64_t wg, int T, int chunk, int c) {
+  const int per_phase = owned_touch_chunks(T, chunk);
+  const int P = c / per_phase, t0 = (c - P * per_phase) * chunk;
+  const OwnedPhase ph = owned_phase(pl, P);
+  const int64_t in_round = owned_round_rows(pl, wg, ph.row_round);
+  const int64_t lds_first = (int64_t)t0 * pl.G * pl.R;
+  int64_t lds_last = lds_first + (int64_t)chunk * pl.G * pl.R;
+  if (lds_last > in_round) lds_last = in_round;
+  OwnedTouchRows r{lds_first < lds_last, ph.slice, 0, 0};
+  if (r.any) {
+    r.r_first = owned_task(pl, wg, ph.row_round, t0, 0).row0;
+    r.r_last = r.r_first + (lds_last - lds_first);
+  }
+  return r;
+}
+
+// The j-th boundary word (a row number of the slice) touched for the rows [r_first, r_last); -1: none, and none after it.
+__host__ __device__ constexpr int64_t owned_touch_boundary(int64_t r_first, int64_t r_last, int64_t j) {
+  return j == 0 ? r_first : (j == 1 ? r_last : (r_first + (j - 1) * kOwnedTouchLineWords <= r_last ? r_first + (j - 1) * kOwnedTouchLineWords : -1));
+}
+
+// The j-th id word touched for the edges [e0, e1); -1: none, and none after it.
+__host__ __device__ constexpr int64_t owned_touch_id(int64_t e0, int64_t e1, int64_t j) {
+  return e0 + j * kOwnedTouchLineWords < e1 ? e0 + j * kOwnedTouchLineWords : -1;
+}
+
+// The chunk whose duty the wave that reserves task k takes (k counts the slots phase-major, as the task counter does);
+// -1: none — a slot that is not the first of a chunk, or one past the last task.
+__host__ __device__ inline int owned_duty_chunk(int k, int T, int chunk, int phases) {
+  if (k < 0 || T < 1 || k >= phases * T) return -1;
+  const int P = k / T, t = k - P * T;
+  return t % chunk == 0 ? P * owned_touch_chunks(T, chunk) + t / chunk : -1;
+}
+
+__host__ __device__ constexpr int owned_duty_lead_chunks(int lead, int chunk) { return (lead + chunk - 1) / chunk; }
+
+// The chunks [first, end) the duty of chunk c touches, of `chunks` = phases x owned_touch_chunks in all.
+struct OwnedDutySpan {
+  int first, end;
+};
+
+__host__ __device__ inline OwnedDutySpan owned_duty_span(int c, int chunks, int lead_chunks) {
+  OwnedDutySpan s{c == 0 ? 0 : c + lead_chunks, c + lead_chunks + 1};
+  if (s.end > chunks) s.end = chunks;
+  if (s.first > s.end) s.first = s.end;
+  return s;
+}
 
 }  // namespace dgmi

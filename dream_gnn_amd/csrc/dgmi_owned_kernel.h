@@ -42,6 +42,25 @@
 // costs more than it buys.  A launch without a gate carries no gate work: no memset of the arrive counters, no counting
 // of a phase's tasks; a kernel built without GATE has no gate code, and nothing in it waits for anything outside its
 // own workgroup.
+//
+// The DUTY form has no toucher: all 16 waves are workers and the touching is a DUTY of task slots (owned_duty_*,
+// dgmi_owned_common.h).  The wave that reserves the first slot of a chunk of `duty_chunk` slots touches, right after the
+// reservation and before anything else — before it requests that task's boundaries, before it runs the task it holds —
+// the same words the toucher touches for the chunk that lies `duty_lead` slots ahead (the first duty also for the
+// chunks in front of that), as many lines per wave-instruction as there are lanes, and then goes on as any worker.  It
+// pays one exposed cold latency per level (the ends of the boundaries, which name the ids, then the ids' lines, which
+// are waited for with whatever the wave waits for next); no other wave pays anything.  A duty waits for NOTHING but its
+// own loads: it polls nothing, reads neither done[] nor the counter nor anything another workgroup writes, and what it
+// loads is read-only for the launch.  So the argument above holds word for word: inside a workgroup the 16 worker
+// waves take tasks from one LDS counter, phase-major then row-major; a wave reserves its next task (does that slot's
+// duty, if it has one, which ends after two load latencies, and requests that task's row boundaries) before it runs the
+// current one.  done[t] is release-stored after a task's LDS writes and acquire-polled before the next one's first LDS
+// access.  The lowest unfinished task never waits (everything before it is finished and a reserved task is only ever
+// held by a wave that runs an earlier one — a wave in a duty holds one reserved task and runs an earlier one, or none:
+// its duty returns and it runs it), so this cannot deadlock.  The order inside a task: reserve the next task, its duty,
+// request its boundaries, wait for done[], touch LDS, wave barrier, release.  The form is built without GATE (the
+// advisory gate lives in the toucher): a launch that asks for a gate takes the form with a toucher.  Nothing of a sum
+// differs: every product is bit for bit the toucher form's.  Measured: profiles/owned_duty/README.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,9 +72,6 @@
 
 namespace dgmi {
 namespace {
-
-constexpr int kOwnedTouchChunk = 4;  // tasks the toucher touches for at a time
-constexpr int kOwnedTouchLead = 8;   // tasks between the counter and the first task of the chunk it touches for
 
 // An fp32 table (columns, load, sums and the canonical step: RowF32, dgmi_sliced_common.h): one float4 of the LPR
 // slots of an LDS row.
@@ -152,7 +168,7 @@ __device__ __forceinline__ float owned_mul_rn(float a, float b) {
 }
 
 // VALS: 0 = unit edge values, 2 = multiplicities in the id words (dgmi_sliced.hip).  WAVES: waves of the workgroup, the
-// last one the toucher.  GATE: the phase gate is built (`arrive`, `lag` and `spin_ticks` are read under it only).
+// last one the toucher (not under DUTY).  GATE: the phase gate is built (`arrive`, `lag` and `spin_ticks` are read under it only).
 //
 // SCALED: the id words carry, in bits kScaleShift .. kScaleShift + kScaleBits - 1, the CODE of the gathered row's scale
 // (dgmi_kernels.h; ids are < 2^kScaleShift): `table[code]` is diag(src_scale)'s entry of that row, so the product is
@@ -162,13 +178,18 @@ __device__ __forceinline__ float owned_mul_rn(float a, float b) {
 // and waits beside the row in a ring of W registers, which the hand-over carries like the row.  The row joins the sum
 // as s * x, rounded once (no contraction with the add or the multiplicity): bit for bit what the pre-scaled table
 // gives.  Nothing else differs: the task protocol, the toucher and write_rows read no id word.
-template <typename Row, int LPR, int VALS, bool OFF32, int WAVES, bool GATE, bool SCALED = false>
+//
+// DUTY: the form without a toucher (at the top of this file): all WAVES waves are workers; `duty_chunk` task slots per
+// duty, which touches `duty_lead` slots ahead.  Built without GATE.
+template <typename Row, int LPR, int VALS, bool OFF32, int WAVES, bool GATE, bool SCALED = false, bool DUTY = false>
 __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, const int32_t* __restrict__ indices,
                                            const typename Row::Elem* __restrict__ X, int64_t ldx,
                                            const float* __restrict__ dst_scale, float* __restrict__ Y, int64_t ldy,
                                            int64_t n_dst, int F, OwnedPlan pl, unsigned* __restrict__ arrive, int lag,
                                            int64_t spin_ticks, int workers, Epilogue ep,
-                                           const float* __restrict__ table = nullptr, int n_codes = 0) {
+                                           const float* __restrict__ table = nullptr, int n_codes = 0, int duty_chunk = 0,
+                                           int duty_lead = 0) {
+  static_assert(!DUTY || !GATE, "the phase gate lives in the toucher");
   typedef typename Row::Elem Elem;
   typedef typename Row::Acc Acc;
   constexpr bool MULT = VALS == 2;
@@ -200,7 +221,7 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
   const int total = pl.phases * T;
   const int label = (int)(blockIdx.x & 7u);
 
-  if (wave == WAVES - 1) {  // ---- the toucher ----
+  if (!DUTY && wave == WAVES - 1) {  // ---- the toucher ----
     const unsigned n_label = (unsigned)((pl.active - label + 7) >> 3);  // active workgroups with this label (>= 1: this one)
     const unsigned* my_arrive = GATE ? arrive + (size_t)label * pl.phases : nullptr;
     // One loop does both jobs and blocks in neither: touch the next chunk of tasks once the counter is within the lead
@@ -340,7 +361,39 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
     }
     v[u] = Row::template load<OFF32>(X, Xcol, word, ldx, row_bytes, cbytes);
   };
+  // The duty of the task slot a wave has just reserved (DUTY; owned_duty_*, dgmi_owned_common.h): wave-uniform, and it
+  // waits for its own loads only — first the two ends of a chunk's boundaries, which name its ids, then nothing: the ids'
+  // lines are waited for with whatever the wave waits for next.  What it reads is read-only for the whole launch.
+  const int duty_chunks = DUTY ? pl.phases * owned_touch_chunks(T, duty_chunk) : 0;
+  const int duty_lead_chunks = DUTY ? owned_duty_lead_chunks(duty_lead, duty_chunk) : 0;
+  auto duty = [&](int slot) {
+    const int c = owned_duty_chunk(slot, T, duty_chunk, pl.phases);
+    if (c < 0) return;
+    const OwnedDutySpan span = owned_duty_span(c, duty_chunks, duty_lead_chunks);
+    int keepalive = 0;
+    for (int cc = span.first; cc < span.end; ++cc) {
+      const OwnedTouchRows tr = owned_touch_rows(pl, wg, T, duty_chunk, cc);
+      if (!tr.any) continue;  // (a short last round)
+      const int32_t* sp_s = segptr + (int64_t)tr.slice * n_dst;
+      int v = 0;  // lane 0: the first boundary, lane 1: the last
+      for (int64_t j = lane;; j += kWave) {
+        const int64_t rp = owned_touch_boundary(tr.r_first, tr.r_last, j);
+        if (rp < 0) break;
+        const int b = sp_s[rp];
+        if (j < 2) v = b;
+        keepalive ^= b;
+      }
+      const int e0 = __builtin_amdgcn_readlane(v, 0), e1 = __builtin_amdgcn_readlane(v, 1);
+      for (int64_t j = lane;; j += kWave) {
+        const int64_t p = owned_touch_id(e0, e1, j);
+        if (p < 0) break;
+        keepalive ^= indices[p];
+      }
+    }
+    asm volatile("" ::"v"(keepalive));  // the loads exist without an instruction of their own
+  };
   int k = grab();
+  if (DUTY) duty(k);
   OwnedWork w = owned_decode(pl, wg, T, k, grp);
   int e_begin = 0, e_end = 0;
   hand_over(boundaries(w), w, e_begin, e_end);
@@ -360,6 +413,7 @@ __device__ __forceinline__ void owned_body(const int32_t* __restrict__ segptr, c
       mults = mults_in;
     }
     const int k_next = grab();
+    if (DUTY) duty(k_next);
     const OwnedWork w_next = owned_decode(pl, wg, T, k_next, grp);
     const int next_b = boundaries(w_next);
     int n_begin = 0, n_end = 0;  // the group's run in the next task

@@ -21,6 +21,9 @@ struct Tuning {
   int sliced_owned_workers = 0;     // DGMI_SLICED_OWNED_WORKERS: worker waves of a workgroup that take tasks, the others leave at once (0: all; 1: one wave runs every task in order; never changes a bit; test)
   int sliced_owned_slices = 0;      // DGMI_SLICED_OWNED_SLICES: slices of the layouts made for the owned form (dgmi_sliced_layout_slices; 0: built-in rule, n: n for every product it can plan — which form then runs on them is still sliced_owned's rule: 1 to run the owned form; a bf16 table, for which no such layout is made, runs the pair while a count is forced)
   int sliced_owned_scaled = -1;    // DGMI_SLICED_OWNED_SCALED: the owned form's scaled kernel (scale codes in the id words, include/dgmi_scale.h) 0 = never, 1 = wherever it is built and the owned form takes the product, -1 = built-in rule (its measured classes; everything it is built for while sliced_owned = 1 forces the form)
+  int sliced_owned_duty = -1;      // DGMI_SLICED_OWNED_DUTY: the owned form without a toucher — sixteen workers, the touching a duty of task slots (dgmi_owned_kernel.h) 0 = never, 1 = wherever it is built (an fp32 table, 32-bit offsets, 16- or 32-lane groups, no gate, one workgroup per CU), -1 = built-in rule (its measured classes)
+  int sliced_owned_duty_chunk = 0;  // DGMI_SLICED_OWNED_DUTY_CHUNK: task slots per duty (0: built-in, a whole phase)
+  int sliced_owned_duty_lead = 0;   // DGMI_SLICED_OWNED_DUTY_LEAD: task slots a duty touches ahead (0: built-in, one chunk)
   int sliced_owned_lag = -2;       // DGMI_SLICED_OWNED_LAG: phases a workgroup may run ahead of its XCD's slowest (-1: no gate, -2: built-in)
   int64_t sliced_owned_spin_ticks = 0;  // DGMI_SLICED_OWNED_SPIN_TICKS: bound of one gate wait, 100 MHz ticks (0: built-in)
   int64_t select_window_min = 0;    // DGMI_SELECT_WINDOW_MIN: shortest list that takes the window passes
